@@ -18,9 +18,23 @@ A "step" is one outer ADMM iteration: the x-update of every node, the halo excha
 test needs (asynchronous, into pinned host memory: run_admm's pipelined mode, DESIGN.md
 section 9).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong C3,C4|none] [--proxy fast|all|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--strong C3,C4|none] [--proxy fast|all|none]
     torchrun --nproc-per-node N bench.py --gpus N ...
     python bench.py --config C2|C3|C4|C5|C5s [--as-rank R/W]
+
+A plain run does only what the headline figure needs: it binds the workload, warms up, times
+the K steps, writes the last step's outputs if ``--dump-outputs`` is given and prints the
+result line (metric, value, unit, ms_per_step, the workload's description).  Everything else
+described below -- the ``weak8`` and ``strong`` legs, the per-rank proxies, the rooflines,
+the CPU baseline, the N > 1 exchange check -- runs only with ``--full``, after the timed steps.
+
+``--dump-outputs DIR`` writes what the last timed step left with its caller as
+``DIR/<name>.npy``: ``x`` (V x n float64, every graph node's image after that step's
+x-update) and ``stats`` (float64, the flat statistics table the stop test reads:
+V x node statistics, then E x edge statistics).  The inputs are seeded, so two runs with the
+same arguments dump the same problem's outputs.  Above 64 MB in all (DUMP_MAX_BYTES) an array
+is cut to a fixed, seeded sample of its elements (dump_outputs).
 
 ``python bench.py --gpus N`` with N > 1 and no WORLD_SIZE in the environment launches
 the N ranks itself (one child process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
@@ -380,6 +394,7 @@ def timed_steps(r, steps, warmup, world, prime=None, markers=False):
         t = torch.tensor([el], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    r["last_stats"] = host  # the last timed step's statistics table (--dump-outputs)
     return el
 
 
@@ -389,6 +404,47 @@ def _stats_local(rg):
     from admm_hip.exchange import assemble_stats_device
     parts = [(nb.plan, nb.node_stats, nb.edge_stats[: len(nb.plan.stored_edges)]) for nb in rg.batches]
     return assemble_stats_device(rg.plan.V_total, len(rg.plan.edges), 1, parts)
+
+
+# ---------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed
+# ---------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 * 10**6  # of .npy data in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write ``arrays`` (name -> float32 / float64 ndarray) as ``out_dir/<name>.npy``.  If they
+    hold more than ``max_bytes`` in all, every array above its equal share of the budget is cut
+    to a sample of its flattened elements: one element from each of k equal consecutive
+    stretches, at a position drawn by a generator seeded with DUMP_SEED (O(k) work whatever the
+    array's size; ascending indices) -- the same for every run with the same shapes, so two
+    builds' dumps compare element for element.  Returns {name: elements written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    share = (max_bytes - 128 * len(arrays)) // len(arrays)  # (128: a .npy header)
+    whole = sum(v.nbytes + 128 for v in arrays.values()) <= max_bytes
+    written = {}
+    for k, v in arrays.items():
+        if not whole and v.nbytes > share:
+            cnt = share // v.itemsize
+            stride = v.size // cnt  # (>= 1: the array is larger than its share)
+            idx = np.arange(cnt, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, cnt)
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+        written[k] = int(v.size)
+    return written
+
+
+def last_step_outputs(r):
+    """The arrays the last timed step left with its caller: every graph node's image (gathered
+    over the ranks at N > 1: a collective, every rank calls) and the statistics table the step
+    read back into pinned host memory."""
+    x = r["rg"].images()
+    return {"x": x.to("cpu").numpy(), "stats": r["last_stats"].numpy().copy()}
 
 
 # ---------------------------------------------------------------------------
@@ -689,6 +745,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: rooflines, "
+                         "CPU baseline, weak8 / strong legs, per-rank proxies, the N > 1 exchange check "
+                         "(off by default: a plain run sets up, warms up, times and prints)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (images x, statistics table stats) as "
+                         "DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fwd-reps", type=int, default=20)
     ap.add_argument("--workload", choices=("auto", "C3", "weak8"), default="auto",
@@ -714,7 +777,8 @@ def main():
                          "rule (stored wherever the edge state fits, admm_hip/plan.py z_is_stored)")
     ap.add_argument("--stored-z", action="store_true", help="= --edge-state stored")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline workload (no weak8, strong or proxy legs): rocprofv3 runs")
+                    help="with --full: only the headline workload and its rooflines (no weak8, strong or "
+                         "proxy legs)")
     args = ap.parse_args()
     if args.headline_only:
         args.strong, args.proxy = "none", "none"
@@ -763,7 +827,8 @@ def main():
     r = setup_run(workload, world, rank, local_rank)
     if world > 1:
         dist.barrier()
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and workload in ("C3", "weak8")
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+                and workload in ("C3", "weak8"))
     first = {}
 
     def prime(nb):  # node 0's first x-update and its inputs, for the CPU parity check
@@ -773,14 +838,14 @@ def main():
 
     el = timed_steps(r, args.steps, args.warmup, world, prime, markers=True)
     plan, geom = r["plan"], r["geom"]
-    # N > 1: the halo rows the last exchange delivered (RCCL p2p / all-gather) must equal the
-    # owners' images byte for byte (checked after the timed region)
-    from admm_hip.exchange import verify_halo
-    xcheck = verify_halo(plan, r["rg"].x_rank) if world > 1 else None
+    if args.dump_outputs:
+        outs = last_step_outputs(r)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+        del outs
     n_img, V_total, dtype = r["n_img"], r["V_total"], r["dtype"]
     value = V_total * args.steps / el
     ms_per_step = 1e3 * el / args.steps
-    roof, roof_fwd, roof_back, tr, tr_file = projector_rooflines(r, workload, args.fwd_reps)
     headline_fixed = workload in CONFIGS  # a fixed-size config (C3 headline, --config)
     result = {
         "metric": "ADMM node-updates/sec (whole node), 512² phantom; rel-Fro vs CPU ref",
@@ -803,10 +868,19 @@ def main():
             "parallelism": f"graph-node shards x{world}",
             "batch_streams": len(r["rg"].streams) if r["rg"].streams else 1,
         },
-        "roofline": roof,
-        "roofline_fwd": roof_fwd,
-        "roofline_back": roof_back,
     }
+    if not args.full:  # a plain run: the headline line alone
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # N > 1: the halo rows the last exchange delivered (RCCL p2p / all-gather) must equal the
+    # owners' images byte for byte (checked after the timed region)
+    from admm_hip.exchange import verify_halo
+    xcheck = verify_halo(plan, r["rg"].x_rank) if world > 1 else None
+    roof, roof_fwd, roof_back, tr, tr_file = projector_rooflines(r, workload, args.fwd_reps)
+    result.update(roofline=roof, roofline_fwd=roof_fwd, roofline_back=roof_back)
     if xcheck is not None:
         result["exchange_check"] = dict(xcheck, backend=backend, mode=r["rg"].halo.mode,
                                         ok=xcheck["mismatched_rows"] == 0)

@@ -13,6 +13,7 @@
 # Every step has its own time limit; the first failing step ends the session.
 set -u
 mkdir -p gpurun_out
+OUT=${ADMM_OUT_DIR:-bench_out}; mkdir -p "$OUT"  # where the bench lines (bench.py --full) are written
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 run() {  # name, limit, command...
@@ -54,8 +55,8 @@ for step in "$@"; do
     envhl=*)  # envhl=VAR=VAL[@WORKLOAD]: headline only (no CPU baseline) with VAR=VAL in the environment
       v=${step#envhl=}; wl=C3; case $v in *@*) wl=${v#*@}; v=${v%@*} ;; esac
       nm=$(echo "$v" | tr '=' '_')
-      env "$v" timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only --workload $wl > gpurun_out/envhl_${nm}_${wl}_${TAG}.json 2> gpurun_out/envhl_${nm}_${wl}_${TAG}.err || { tail -5 gpurun_out/envhl_${nm}_${wl}_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/envhl_${nm}_${wl}_${TAG}.json ;;
+      env "$v" timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --headline-only --workload $wl > $OUT/envhl_${nm}_${wl}_${TAG}.json 2> $OUT/envhl_${nm}_${wl}_${TAG}.err || { tail -5 $OUT/envhl_${nm}_${wl}_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/envhl_${nm}_${wl}_${TAG}.json ;;
     prof|profm|profd)  # prof: default modes; profm / profd: mirror-mode forward forced on / off
       mm=; [ $step = profm ] && mm=1; [ $step = profd ] && mm=0
       ADMM_FWD_MIRROR=$mm run $step 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${step}_${TAG} -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --headline-only > gpurun_out/${step}_${TAG}.log 2>&1 || exit 1
@@ -65,29 +66,29 @@ for step in "$@"; do
       ADMM_TOMO_LIB=$lib run $step 300 rocprofv3 --kernel-trace --stats -d gpurun_out/profvar_${v}_${TAG} -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --headline-only > gpurun_out/profvar_${v}_${TAG}.log 2>&1 || exit 1
       python scripts/top_kernels.py gpurun_out/profvar_${v}_${TAG} > gpurun_out/profvar_${v}_${TAG}.txt; head -8 gpurun_out/profvar_${v}_${TAG}.txt ;;
     bench)
-      run bench 600 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { tail -5 gpurun_out/bench_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/bench_${TAG}.json ;;
+      run bench 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err || { tail -5 $OUT/bench_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/bench_${TAG}.json ;;
     benchall)
-      run benchall 900 python bench.py --steps 20 --warmup 5 --proxy all > gpurun_out/benchall_${TAG}.json 2> gpurun_out/benchall_${TAG}.err || { tail -5 gpurun_out/benchall_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/benchall_${TAG}.json ;;
+      run benchall 900 python bench.py --full --steps 20 --warmup 5 --proxy all > $OUT/benchall_${TAG}.json 2> $OUT/benchall_${TAG}.err || { tail -5 $OUT/benchall_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/benchall_${TAG}.json ;;
     hl|hl2|hl4|hlm|hlm2)  # quick headline A/B (no CPU baseline): --streams 1/2/4; m = ADMM_FWD_MIRROR=1
       st=1; case $step in *2) st=2 ;; *4) st=4 ;; esac
       mm=0; case $step in hlm*) mm=1 ;; esac
-      ADMM_FWD_MIRROR=$mm run $step 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only --streams $st > gpurun_out/${step}_${TAG}.json 2> gpurun_out/${step}_${TAG}.err || { tail -5 gpurun_out/${step}_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/${step}_${TAG}.json ;;
+      ADMM_FWD_MIRROR=$mm run $step 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --headline-only --streams $st > $OUT/${step}_${TAG}.json 2> $OUT/${step}_${TAG}.err || { tail -5 $OUT/${step}_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/${step}_${TAG}.json ;;
     var=*)  # var=NAME[@WORKLOAD]: headline (C3 or weak8) with the tuning build variants/lib_NAME.so
             # (scripts/sweep_build.py; NAME "base": the in-tree library), default modes
       v=${step#var=}; wl=C3; case $v in *@*) wl=${v#*@}; v=${v%@*} ;; esac
       lib=variants/lib_$v.so; [ $v = base ] && lib=
-      ADMM_TOMO_LIB=$lib run $step 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only --workload $wl > gpurun_out/var_${v}_${wl}_${TAG}.json 2> gpurun_out/var_${v}_${wl}_${TAG}.err || { tail -5 gpurun_out/var_${v}_${wl}_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/var_${v}_${wl}_${TAG}.json ;;
+      ADMM_TOMO_LIB=$lib run $step 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --headline-only --workload $wl > $OUT/var_${v}_${wl}_${TAG}.json 2> $OUT/var_${v}_${wl}_${TAG}.err || { tail -5 $OUT/var_${v}_${wl}_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/var_${v}_${wl}_${TAG}.json ;;
     plan=*)  # plan=K[:m]: headline with the forward plan forced to K (ADMM_FWD_PLAN; m: mirror mode)
       v=${step#plan=}; mm=0; case $v in *:m) mm=1; v=${v%:m} ;; esac
-      ADMM_FWD_PLAN=$v ADMM_FWD_MIRROR=$mm run $step 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only > gpurun_out/plan_${v}_${mm}_${TAG}.json 2> gpurun_out/plan_${v}_${mm}_${TAG}.err || { tail -5 gpurun_out/plan_${v}_${mm}_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/plan_${v}_${mm}_${TAG}.json ;;
+      ADMM_FWD_PLAN=$v ADMM_FWD_MIRROR=$mm run $step 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --headline-only > $OUT/plan_${v}_${mm}_${TAG}.json 2> $OUT/plan_${v}_${mm}_${TAG}.err || { tail -5 $OUT/plan_${v}_${mm}_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/plan_${v}_${mm}_${TAG}.json ;;
     benchallm)  # benchall with the mirror-mode forward
-      ADMM_FWD_MIRROR=1 run benchallm 900 python bench.py --steps 20 --warmup 5 --proxy all --no-cpu-baseline > gpurun_out/benchallm_${TAG}.json 2> gpurun_out/benchallm_${TAG}.err || { tail -5 gpurun_out/benchallm_${TAG}.err; exit 1; }
-      python scripts/summarize_bench.py gpurun_out/benchallm_${TAG}.json ;;
+      ADMM_FWD_MIRROR=1 run benchallm 900 python bench.py --full --steps 20 --warmup 5 --proxy all --no-cpu-baseline > $OUT/benchallm_${TAG}.json 2> $OUT/benchallm_${TAG}.err || { tail -5 $OUT/benchallm_${TAG}.err; exit 1; }
+      python scripts/summarize_bench.py $OUT/benchallm_${TAG}.json ;;
     share=*)  # share=CONFIG:R/W[:d]: one rank's share on this GPU (bench --as-rank; d: --edge-state derived A/B)
       v=${step#share=}; cfg=${v%%:*}; rest=${v#*:}; rw=${rest%%:*}; sz=()
       case $rest in *:d) sz=(--edge-state derived) ;; esac

@@ -120,3 +120,34 @@ def test_committed_traffic_matches_kernel_sources():
         bench.TRAFFIC_STALE.clear()
         tr, f = bench.pmc_traffic(wl)
         assert tr is not None, bench.TRAFFIC_STALE
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """``--dump-outputs``: arrays within the byte budget are written whole; above it an array
+    larger than its equal share is cut to a seeded, ascending sample of its elements -- the same
+    indices on every call, so two dumps compare element for element."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_MAX_BYTES <= 64 * 2**20
+    x = np.arange(5000, dtype=np.float64).reshape(5, 1000)
+    st = np.arange(30, dtype=np.float64)
+    w = bench.dump_outputs(str(tmp_path / "whole"), {"x": x, "stats": st})
+    assert w == {"x": 5000, "stats": 30}
+    assert np.array_equal(np.load(tmp_path / "whole" / "x.npy"), x)
+    assert np.array_equal(np.load(tmp_path / "whole" / "stats.npy"), st)
+    for tag in ("s1", "s2"):
+        w = bench.dump_outputs(str(tmp_path / tag), {"x": x, "stats": st}, max_bytes=8192)
+        assert w["stats"] == 30 and 0 < w["x"] < 5000
+    a, b = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s2" / "x.npy")
+    assert np.array_equal(a, b) and a.ndim == 1 and np.all(np.diff(a) > 0)  # x holds its own indices
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in ("x.npy", "stats.npy"))
+    assert total <= 8192
+
+
+def test_plain_and_full_options_parse():
+    """``--full`` and ``--dump-outputs`` exist (a launcher mismatch is still the error reported)."""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--dump-outputs", "unused"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=120,
+                       env=_env(WORLD_SIZE="3", RANK="0", LOCAL_RANK="0"))
+    assert p.returncode == 2 and "must match" in p.stderr

@@ -1,6 +1,6 @@
 """GPU: bench.py keeps the driver contract -- one JSON line on stdout with the metric,
-the whole-job value, timing fields, roofline and (optionally) the CPU baseline and the
-strong-scaling line (task contract)."""
+the whole-job value and timing fields; with ``--full`` also the roofline and (optionally)
+the CPU baseline and the strong-scaling line (task contract)."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def _run(*args, env=None):
 
 
 def test_bench_line_contract(cuda):
-    b = _run("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--strong", "none", "--proxy", "none")
+    b = _run("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--strong", "none", "--proxy", "none")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
               "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in b, k
@@ -62,7 +62,7 @@ def test_bench_launches_its_own_ranks(cuda):
     this one-GPU box; the driver's nccl default is unchanged) and relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ADMM_DIST_BACKEND"] = "gloo"
-    b = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--strong", "none", env=env)
+    b = _run("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--strong", "none", env=env)
     assert b["n_gpus"] == 2 and b["config"]["nodes"] == 16 and b["scaling"] == "weak"
     assert b["exchange_check"]["ok"] and b["exchange_check"]["halo_rows"] == 4
 
@@ -75,7 +75,7 @@ def test_bench_eight_ranks_with_strong_c4(cuda):
     rank) over the same 8 ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ADMM_DIST_BACKEND"] = "gloo"
-    b = _run("--gpus", "8", "--steps", "1", "--warmup", "1", "--strong-steps", "1", env=env)
+    b = _run("--full", "--gpus", "8", "--steps", "1", "--warmup", "1", "--strong-steps", "1", env=env)
     assert b["n_gpus"] == 8 and b["config"]["nodes"] == 64
     assert b["exchange_check"]["ok"] and b["exchange_check"]["mode"] == "p2p"
     assert [s["config"] for s in b["strong"]] == ["C3", "C4"]
@@ -108,7 +108,8 @@ def test_bench_default_proxies(cuda):
     and the weak headline on 8, each with its measured one-GPU time, the share's time and the
     predicted speedup.  (ADMM_TEST_LONG:
     the driver's own default bench run produces this line every round.)"""
-    b = _run("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--strong-steps", "1", "--proxy-steps", "1")
+    b = _run("--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--strong-steps", "1", "--proxy-steps",
+             "1")
     px = b["proxy_8gpu"]
     assert set(k for k in px if "@" in k) == {"C3@2", "C4@2", "C4@4", "C4@8", "C5@8", "weak8@8"}
     w = px["weak8@8"]  # the N = 8 weak headline: 64 nodes, 8 per rank
@@ -121,3 +122,41 @@ def test_bench_default_proxies(cuda):
         assert all(s["ms_per_step"] > 0 for s in p["shares"])
     assert px["C3@2"]["T1_ms_per_step"] == b["ms_per_step"]  # the headline is C3 on this GPU
     assert px["C4@8"]["shares"][0]["vb"] == 4 and px["C3@2"]["shares"][0]["exchange"]["mode"] == "p2p"
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(cuda, tmp_path):
+    """A plain run (no ``--full``) prints the headline line alone -- no roofline, CPU baseline,
+    weak8 / strong legs or proxies -- and ``--dump-outputs`` writes the images and statistics
+    table of the LAST timed step: ``--steps 2 --warmup 1`` is three outer iterations, and the
+    dump equals, bit for bit, the third iteration of the same seeded problem run in this process
+    (and differs from its second).  C2: 8-node ring at 256^2."""
+    import numpy as np
+    import bench
+    from admm_hip import _lib
+    d = tmp_path / "dump"
+    b = _run("--config", "C2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in b, k
+    for k in ("roofline", "roofline_fwd", "roofline_back", "cpu_baseline", "weak8", "strong", "proxy_8gpu",
+              "step_hbm", "exchange_check"):
+        assert k not in b, k
+    assert b["steps"] == 2 and b["ms_per_step"] > 0
+    assert abs(b["value"] - b["config"]["nodes"] * 1e3 / b["ms_per_step"]) <= 1e-6 * b["value"]
+    assert sorted(f.name for f in d.iterdir()) == ["stats.npy", "x.npy"]
+    x, st = np.load(d / "x.npy"), np.load(d / "stats.npy")
+    assert x.shape == (8, 256 * 256) and x.dtype == np.float64 and st.dtype == np.float64
+    assert x.nbytes + st.nbytes <= 64e6
+    # node statistics first (NODE_STATS per node), then EDGE_STATS per edge of the 8-node ring
+    assert st.shape == (8 * _lib.NODE_STATS + 8 * _lib.EDGE_STATS,)
+    assert np.isfinite(x).all() and np.isfinite(st).all() and np.linalg.norm(x) > 0
+    # the same problem here: two iterations, then the third by hand (one step of bench.timed_steps)
+    r = bench.setup_run("C2", 1, 0, 0)
+    rg = r["rg"]
+    bench.timed_steps(r, 1, 1, 1)
+    second = bench.last_step_outputs(r)
+    assert not np.array_equal(second["x"], x) and not np.array_equal(second["stats"], st)
+    rg.node_update()
+    rg.exchange_consensus()
+    third_stats = rg.stats_device().to("cpu").numpy()
+    assert np.array_equal(rg.images().to("cpu").numpy(), x)
+    assert np.array_equal(third_stats, st)
