@@ -27,6 +27,10 @@ ADMM_MASK_CHAIN = 2
 ADMM_Q_ARITHMETIC = 0
 ADMM_Q_HARMONIC = 1
 MASK_MAX_NODES = 64
+ADMM_FBP_RAMLAK = 0
+ADMM_FBP_SHEPP_LOGAN = 1
+ADMM_FBP_HANN = 2
+FBP_MAX_DET = 4096
 NODE_STATS = 6  # mse_sino, |g|^2, TV, quad, img, split-Bregman stationarity residual^2
 EDGE_STATS = 3  # |x_a-z|^2, |x_b-z|^2, |dz|^2
 
@@ -117,6 +121,8 @@ SYMBOLS = {
                          C.c_void_p, C.c_void_p],
     "admm_chain_orders": [C.POINTER(C.c_uint64), C.c_int, C.c_uint32, C.c_int, C.c_int64, C.c_void_p,
                           C.POINTER(C.c_uint64)],
+    "admm_fbp_filter": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                        C.c_int, C.c_void_p],
 }
 
 _lock = threading.Lock()

@@ -39,6 +39,7 @@ import torch
 import torch.distributed as dist
 
 from .exchange import split_stats
+from .fbp import FILTERS, fbp
 from .geometry import RayTransform
 from .groups import RankGroups
 from .matrix import MatrixOperator, as_operators
@@ -87,8 +88,14 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              cg_iters=5, tv_kind="iso", group=None, return_tensors=False, timing=None,
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
-             pipeline=None, streams=1, edge_state=None):
-    """``edge_state``: "stored" / "derived" z (None: the run's rule, plan.z_is_stored --
+             pipeline=None, streams=1, edge_state=None, x_init=None):
+    """``x_init``: where the run starts.  None: x = 0, z = 0 (the reference, _ver2:35-43).
+    "fbp" or "fbp:<filter>" (admm_hip.fbp.FILTERS): node g starts from the filtered back
+    projection of its own sinogram, ``A_g.fbp(sinograms[g], filter)``.  A list, array or tensor of
+    one image per graph node, (N, N) or (n,): node g starts from entry g (converted to float64).
+    Either way the run is a fresh ADMM around those images: y = 0, d = e = 0 and
+    z_e = (x_a + x_b) / 2 (weighted fusion: the W-weighted mean) -- groups.RankGroups.start_from.
+    ``edge_state``: "stored" / "derived" z (None: the run's rule, plan.z_is_stored --
     stored wherever it fits; ADMM_EDGE_STATE in the environment forces it too).
 ``inner_chunks``: split each x-update into warm-started solves of these round counts
     (block_6_admm_loop.py:14-69 chunked SCS); ``chunk_snapshot_dir`` then receives that
@@ -121,6 +128,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     mu = DEFAULT_MU_FACTOR * lam_tv if mu is None else float(mu)
     if not mu > 0:
         raise ValueError("mu must be > 0 (set lam_tv > 0 or pass mu explicitly)")
+    start = _parse_x_init(x_init, A_dense_list, V_total, N)  # argument errors on every rank alike
     world, rank = _dist_info(group)
     torch.cuda.set_device(A_dense_list[0].device)
     if snapshot_dir is not None:
@@ -133,6 +141,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                     derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state])
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
+    if start is not None:
+        rg.start_from(_initial_images(start, A_dense_list, sinograms, plan.local_nodes, rg.device))
     if world > 1:
         dist.barrier(group=group)
     hist = {k: [] for k in HISTORY_KEYS + EXTRA_KEYS}
@@ -211,6 +221,52 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         return [X[i] for i in range(V_total)], hist
     Xh = X.to("cpu").numpy()
     return [Xh[i].copy() for i in range(V_total)], hist
+
+
+def _parse_x_init(x_init, A_list, V_total, N):
+    """Validate ``x_init`` (run_admm) without device work: None, ("fbp", filter) or
+    ("images", [V_total entries])."""
+    if x_init is None:
+        return None
+    if isinstance(x_init, str):
+        kind, _, filt = x_init.partition(":")
+        filt = filt or "ram-lak"
+        if kind != "fbp" or filt not in FILTERS:
+            raise ValueError(f"x_init must be None, 'fbp', 'fbp:<filter>' with a filter of {FILTERS}, "
+                             f"or one image per node; got {x_init!r}")
+        for g, A in enumerate(A_list):
+            if not isinstance(A, RayTransform):
+                raise ValueError(f"x_init='fbp': node {g} has an explicit-matrix operator, which has no "
+                                 "detector axis to filter along")
+        return ("fbp", filt)
+    if isinstance(x_init, (torch.Tensor, np.ndarray)):
+        if x_init.ndim < 2:
+            raise ValueError(f"x_init needs one image per graph node ({V_total}), got shape {tuple(x_init.shape)}")
+    imgs = list(x_init)
+    if len(imgs) != V_total:
+        raise ValueError(f"x_init has {len(imgs)} images, the graph has {V_total} nodes")
+    for g, im in enumerate(imgs):
+        size = im.numel() if isinstance(im, torch.Tensor) else np.asarray(im).size
+        if size != N * N:
+            raise ValueError(f"x_init image of node {g} has {size} entries, expected {N} x {N} = {N * N}")
+    return ("images", imgs)
+
+
+def _initial_images(start, A_list, sinograms, local_nodes, dev):
+    """{g: float64 (n,) device tensor} for this rank's nodes from a parsed ``x_init``."""
+    kind, arg = start
+    out = {}
+    for g in local_nodes:
+        if kind == "fbp":
+            A = A_list[g]
+            s = sinograms[g]
+            s = s if isinstance(s, torch.Tensor) else torch.as_tensor(np.asarray(s))
+            im = fbp(A, s.reshape(-1), arg)
+        else:
+            im = arg[g]
+            im = im if isinstance(im, torch.Tensor) else torch.as_tensor(np.asarray(im))
+        out[g] = im.reshape(-1).to(device=dev, dtype=torch.float64)
+    return out
 
 
 def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose):

@@ -201,6 +201,11 @@ class RayTransform:
                    "admm_column_norms_sq")
         return W.cpu().numpy() if as_numpy else W
 
+    def fbp(self, y, filter: str = "ram-lak"):
+        """Filtered back projection of the sinogram(s) ``y`` (admm_hip.fbp.fbp)."""
+        from .fbp import fbp
+        return fbp(self, y, filter)
+
     def __repr__(self) -> str:
         t = ".T" if self._adjoint else ""
         return f"RayTransform{t}(N={self.geom.N}, angles={self.geom.n_angles}, {self.dtype})"

@@ -246,6 +246,18 @@ class RankGroups:
             if hal.numel():
                 torch.index_select(self.x_rank, 0, hal, out=nb.x_ext[nb.V:])
 
+    def start_from(self, images) -> None:
+        """Start the run from the images ``images[g]`` (float64 (n,) device tensors; at least this
+        rank's nodes) instead of x = 0: a fresh ADMM around a consistent (x, z) with zero duals
+        (NodeBatch.start_edges).  The local rows are written, every halo and cross-batch row is
+        filled by ``exchange()`` -- bitwise its owner's image on every rank -- and each batch then
+        forms z (or x_prev) from its x_ext rows.  Collective over the ranks of a distributed run."""
+        for nb in self.batches:
+            nb.set_local_images(images)
+        self.exchange()
+        for nb in self.batches:
+            nb.start_edges()
+
     def consensus(self) -> None:
         self._concurrent(lambda nb: nb.consensus())
 

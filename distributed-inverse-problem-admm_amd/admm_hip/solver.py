@@ -170,6 +170,34 @@ class NodeBatch:
         torch.cuda.synchronize(self.dev)
         _lib.check(self.lib.admm_batch_bind(self.ctx.h, C.byref(self.cb)), "admm_batch_bind")
 
+    def set_local_images(self, images) -> None:
+        """Local rows of x_ext <- ``images[g]`` (float64 (n,) device tensors by global node)."""
+        for r, g in enumerate(self.plan.local_nodes):
+            self.x_ext[r].copy_(images[g])
+
+    def start_edges(self) -> None:
+        """A fresh ADMM state around the current x_ext (halo rows included): zero duals and
+        split-Bregman variables, z_e = (x_a + x_b) / 2 (weighted fusion: (W_a x_a + W_b x_b) /
+        (W_a + W_b)); derived z: x_prev = x_ext.  Elementwise torch expressions of the endpoint
+        rows, so every batch and rank that stores an edge forms the same z bitwise.  The library
+        projects x again in the first update after a bind, so keep_x batches start correctly."""
+        self.d.zero_()
+        self.e.zero_()
+        self.y.zero_()
+        if self.y_b is not None:
+            self.y_b.zero_()
+        if self.x_prev is not None:
+            self.x_prev.copy_(self.x_ext)
+        if self.z is None:
+            return
+        x, w = self.x_ext, self.w
+        for k in range(len(self.plan.stored_edges)):  # one edge at a time: no [E][n] temporaries
+            a, b = self.plan.edge_a_row[k], self.plan.edge_b_row[k]
+            if self.fusion == "weighted":
+                self.z[k] = (w[a] * x[a] + w[b] * x[b]) / (w[a] + w[b])
+            else:
+                self.z[k] = (x[a] + x[b]) * 0.5
+
     def z_of(self, k: int) -> torch.Tensor:
         """z of stored edge slot k: the stored vector, or (derived) the midpoint of its endpoint
         rows of x_prev -- the value every kernel forms."""

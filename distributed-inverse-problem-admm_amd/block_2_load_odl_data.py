@@ -25,7 +25,11 @@ matrix-free:
   (A_agg^T A_agg + 1e-3 I)^{-1} A_agg^T agg_sinogram as an (N, N) array
   (block_2_test.py:83-88), solved by CG on the GPU (admm_hip.data.ridge_ls); computed when
   the call uses the legacy surface (``base_dir=``) or ``agg_ls=True``, else None;
-  ``agg_fbp_recon`` -- None, as the legacy loader leaves it (:77).
+  ``agg_fbp_recon`` -- None by default, as the legacy loader leaves it (block_2_test.py:77,
+  "ODL only for optional FBP reconstruction", :11); with ``agg_fbp=True`` the (N, N) filtered
+  back projection of ``agg_sinogram`` through the aggregate operator (admm_hip.fbp.fbp,
+  ramp filter ``fbp_filter``: "ram-lak", "shepp-logan" or "hann"); ``agg_sinogram`` is returned
+  unchanged.
 
 Operator hand-off (block_2 -> block_3).  With ``build_dense`` the reference pickles the
 dense list into ``save_operators_dir/A_dense_list.pkl`` (:197-201) and block_3 reads it
@@ -53,6 +57,7 @@ from datetime import datetime
 import numpy as np
 
 from admm_hip.data import make_sinograms, ridge_ls, shepp_logan
+from admm_hip.fbp import fbp
 from admm_hip.geometry import ParallelBeamGeometry, RayTransform, default_device
 from admm_hip.opfile import load_operators, save_operators
 from admm_hip.solver import make_operators
@@ -65,7 +70,7 @@ def load_odl_data(N=128, num_nodes=5, noise_level=0.005, output_dir=None, make_p
                   angles_total=None, dtype="float32", device=None, seed=1000, *, base_dir=None,
                   ray_transforms_pickle="ray_transforms.pkl", A_dense_list_pickle="A_dense_list.pkl",
                   agg_op_pickle="aggregate_op.pkl", A_agg_pickle="A_agg.pkl", agg_ls=None,
-                  ls_max_iters=2000):
+                  ls_max_iters=2000, agg_fbp=None, fbp_filter="ram-lak"):
     """block_2_load_odl_data.py:99-253 (and block_2_test.py:15-167 when ``base_dir`` is given)."""
     del make_plots, show_plots, ray_transforms_pickle, agg_op_pickle, A_agg_pickle
     if device is None:
@@ -112,6 +117,10 @@ def load_odl_data(N=128, num_nodes=5, noise_level=0.005, output_dir=None, make_p
     if agg_ls or (agg_ls is None and legacy):
         x_ls, _, _ = ridge_ls(agg, agg_sinogram, 1e-3, max_iters=ls_max_iters)
         ls = x_ls.to("cpu").numpy().reshape(N, N)
+    fbp_recon = None
+    if agg_fbp:
+        x_fbp = fbp(agg, np.ascontiguousarray(agg_sinogram).reshape(-1), fbp_filter)
+        fbp_recon = x_fbp.reshape(N, N)
     return {
         "A_dense_list": ops,
         "sinograms": sinos,
@@ -124,7 +133,7 @@ def load_odl_data(N=128, num_nodes=5, noise_level=0.005, output_dir=None, make_p
         "output_dir": output_dir,
         "phantom": phantoms[0],
         "phantoms": phantoms,
-        "agg_fbp_recon": None,
+        "agg_fbp_recon": fbp_recon,
         "agg_ls_recon": ls,
         "A_dense_list_path": (os.path.join(save_operators_dir, os.path.splitext(A_dense_list_pickle)[0] + ".json")
                               if build_dense and save_operators_dir is not None else None),

@@ -17,6 +17,10 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 eps_try = min(1e-2, eps_target), accept if ||g|| <= eps_target, else
                 eps_try /= 5, at most twice; see admm_hip/admm.py)
 * ``max_inner_updates``  x-updates per tolerance solve in "reference" mode (default 10)
+* ``x_init``    None (default: x = 0, z = 0 as the reference starts, :35-43), "fbp" /
+                "fbp:<filter>" (node g starts from the filtered back projection of its own
+                sinogram, admm_hip/fbp.py) or one image per graph node ((N, N) or (n,)); the
+                run is then a fresh ADMM around those images (y = 0, z = edge means)
 
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
@@ -33,7 +37,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        snapshot_every=None, snapshot_div=10, phantom_true=None,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
-                       max_inner_updates=10):
+                       max_inner_updates=10, x_init=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
     del max_inner_iters  # accepted but unused, as in the reference (_ver2:17)
     return run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=lam_tv, rho=rho,
@@ -42,4 +46,4 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     snapshot_div=snapshot_div, phantom_true=phantom_true, mu=mu,
                     tv_iters=tv_iters, cg_iters=cg_iters, tv_kind=tv_kind, group=group,
                     write_params=write_params, fusion=fusion, inner_tol=inner_tol,
-                    max_inner_updates=max_inner_updates)
+                    max_inner_updates=max_inner_updates, x_init=x_init)

@@ -273,6 +273,25 @@ int admm_pixel_masks(const double* W, int V, int64_t n, int strategy, int k, int
 int admm_chain_orders(const uint64_t pcg[4], int has_uint32, uint32_t uinteger, int V, int64_t n,
                       int32_t* orders, uint64_t pcg_out[6]);
 
+/* --- filtered back projection: the ramp filter (setup) --- */
+
+#define ADMM_FBP_RAMLAK 0      /* h[0] = 1/(4 tau^2), h[k] = -1/(pi^2 k^2 tau^2) for odd k, else 0 */
+#define ADMM_FBP_SHEPP_LOGAN 1 /* h[k] = -2/(pi^2 tau^2 (4 k^2 - 1))                               */
+#define ADMM_FBP_HANN 2        /* h[k] = rl[k]/2 + (rl[k-1] + rl[k+1])/4, rl the Ram-Lak taps      */
+
+/* out[v][t][j] = scale * det_spacing * sum_k sino[v][t][k] * h[j-k],  v < nimg, t < n_angles, j,k < n_det.
+ * dtype = ADMM_DTYPE_* of sino and out (device pointers, sinogram layout of this header); out != sino.
+ * The filter step of the "optional FBP reconstruction" the reference's legacy loader reserves a key
+ * for and leaves empty (block_2_test.py:11,77: agg_fbp_recon = None); the back projection is
+ * admm_project_adj, with scale = dtheta * det_spacing / h^2 turning A^T into the back projection
+ * integral (admm_hip/fbp.py).  tau = det_spacing; sums in float64 (explicit fma, ascending k), rounded
+ * once to dtype, so a row's result does not depend on nimg or on its place in the batch.  Context-free
+ * like admm_pixel_masks; 1 <= n_det <= 4096, nimg * n_angles * n_det < 2^31.  Asynchronous on `stream`
+ * (current device).  Added without an ABI bump: ADMM_ABI_VERSION stays 9 -- the change is additive
+ * (one new function, no struct or existing signature changes). */
+int admm_fbp_filter(const void* sino, void* out, int dtype, int n_angles, int n_det, int nimg,
+                    double det_spacing, double scale, int filter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
