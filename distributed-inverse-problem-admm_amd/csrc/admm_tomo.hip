@@ -148,10 +148,14 @@ struct admm_ctx {
   // windows with one lane block per block, "dma2" two lane blocks per block wherever the lane
   // blocks pair up; default: LDS-DMA, two lane blocks per block where the grid still fills the chip
   int bk_staging = 0;   // 0 default, 1 reg, 2 dma1, 3 dma2
+  // ADMM_BK_EPI at creation (A/B, tests): where the LDS-DMA mirror back projectors' float32 H
+  // epilogue reads its p stencil: "lds" a tile staged in the window LDS after the taps (the
+  // default), "global" per-pixel global loads; the same results bit for bit
+  bool bk_epi_lds = true;
   int n_cu = 0;         // compute units of the device
   admm_ctx* half = nullptr;
   Buf xs, xsT, p, pT, Hp, sino, bI, fpart, r, c, d2, e2;
-  Buf dsumS;  // D = sum_j q_ij as interleaved samples (BACK_H epilogue)
+  Buf dsumS;  // rho D, D = sum_j q_ij, as interleaved samples (BACK_H epilogue)
   Buf x2, p2; // ping-pong partners of x (local rows) and p for the fused TV update
   Buf pring;  // CG direction slots 1 .. K-1 (direction ring; slot 0 = p, slot K = p2)
   Buf ats;    // A^T (A xs - b) of the last update's final x (ADMM_BATCH_KEEP_X)
@@ -539,8 +543,18 @@ int launch_back(admm_ctx* C, BackArgs<T> a, int V, hipStream_t s) {
           // two lane blocks per block while half the blocks still give every CU one
           const bool fills = (long)grid.x * grid.y * grid.z >= 2L * C->n_cu;
           if (grid.z % 2 == 0 && (C->bk_staging == 3 || (C->bk_staging == 0 && fills))) {
-            hipLaunchKernelGGL((k_back_mirror_2<T, VBV, VB>), dim3(grid.x, grid.y, grid.z / 2), dim3(kBkThreads), 0,
-                               s, a);
+            if (C->bk_epi_lds)
+              hipLaunchKernelGGL((k_back_mirror_2<T, VBV, VB>), dim3(grid.x, grid.y, grid.z / 2),
+                                 dim3(kBkThreads), 0, s, a);
+            else
+              hipLaunchKernelGGL((k_back_mirror_2_gepi<T, VBV, VB>), dim3(grid.x, grid.y, grid.z / 2),
+                                 dim3(kBkThreads), 0, s, a);
+            done = true;
+          }
+        }
+        if constexpr (std::is_same<T, float>::value) {
+          if (!done && !C->bk_epi_lds) {
+            hipLaunchKernelGGL((k_back_mirror_gepi<T, VBV, VB, MODE>), grid, dim3(kBkThreads), 0, s, a);
             done = true;
           }
         }
@@ -983,6 +997,8 @@ int admm_ctx_create(admm_ctx** out, const admm_geom* geom, int dtype, int max_im
     const char* st = getenv("ADMM_BK_STAGING");
     const std::string v = st ? st : "";
     C->bk_staging = v == "reg" ? 1 : v == "dma1" ? 2 : v == "dma2" ? 3 : 0;
+    const char* ep = getenv("ADMM_BK_EPI");
+    C->bk_epi_lds = !(ep && std::string(ep) == "global");
   }
   HIPCHK(hipDeviceGetAttribute(&C->n_cu, hipDeviceAttributeMultiprocessorCount, device));
   C->max_images = max_images;
@@ -1483,17 +1499,18 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
   RET(ensure(C->partE, (size_t)3 * std::max(1, B.n_edges) * C->P_edge * 8));
   RET(ensure(C->redH, (size_t)5 * V * 8 * std::max(1, std::min(B.cg_iters, kMaxCgRing))));
   C->bound = true;
-  // D = sum_j q_ij as interleaved samples of the sample dtype (the BACK_H epilogue's rho D p
-  // term): setup data, packed once here rather than in every x-update
+  // rho D, D = sum_j q_ij, as interleaved samples of the sample dtype (the BACK_H epilogue's
+  // rho D p term): setup data, packed and scaled once here rather than in every x-update (rho
+  // is the bound batch's; a re-bind packs again)
   RET(with_vb(C->vb, [&](auto vbc) {
     constexpr int VB = decltype(vbc)::value;
     const int nch = (V + VB - 1) / VB;
     if (C->dtype == ADMM_DTYPE_F32)
       hipLaunchKernelGGL((k_pack_d<float, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap,
-                         B.dsum, (float*)C->dsumS.p, (int)npix, V);
+                         B.dsum, (float*)C->dsumS.p, (int)npix, V, B.rho);
     else
       hipLaunchKernelGGL((k_pack_d<double, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap,
-                         B.dsum, (double*)C->dsumS.p, (int)npix, V);
+                         B.dsum, (double*)C->dsumS.p, (int)npix, V, B.rho);
     CHECK_LAUNCH();
     return ADMM_OK;
   }));

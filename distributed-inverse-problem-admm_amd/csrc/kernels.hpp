@@ -1346,7 +1346,7 @@ struct BackArgs {
   const T* pin;             // H: p;  INIT: xs (interleaved)
   const double* r;          // H: r
   const double* dsum;       // [V][n]
-  const T* dsum_s;          // H: D as interleaved samples [C][n][VB] (one VB-vector per pixel)
+  const T* dsum_s;          // H: rho D as interleaved samples [C][n][VB] (one VB-vector per pixel)
   const double* atb;        // INIT
   const double* cvec;       // INIT, DIAG: c = sum_j q v
   const double* dvar;       // INIT: d [V][2][n]
@@ -1410,13 +1410,33 @@ __device__ __forceinline__ double kt_w_at(const double* __restrict__ d, const do
   return s;
 }
 
+// Where the float32 H epilogue reads p at (i, j) (the pixel and its four stencil neighbours):
+// PGlobal: the interleaved p samples in global memory; PTile: a tile of 16-byte slots (one
+// lane block's VB samples of a pixel) staged in LDS, PITCH slots per row, slot (0, 0) = pixel
+// (i0, j0) -- the same values, so the epilogue's results do not depend on the source.
+struct PGlobal {};
+template <typename T, int VB, int PITCH>
+struct PTile {
+  static_assert(sizeof(Pack<T, VB>) == 16, "one 16-byte slot per pixel");
+  const __attribute__((address_space(3))) char* base;
+  int i0, j0;
+  __device__ __forceinline__ void load(int i, int j, T (&o)[VB]) const {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // one ds_read_b128
+    const u32x4 k =
+        *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(base + ((i - i0) * PITCH + (j - j0)) * 16);
+    __builtin_memcpy(o, &k, 16);
+  }
+};
+
 // Fused epilogue of one pixel: writes the mode's per-pixel outputs and stores the pixel's
 // reduction terms into pq (ACC: adds them, the second pixel of a mirror pair; the caller
 // zero-fills pq, so out-of-image pixels and dead lanes contribute 0).
 // VS / lo (mirror mode): the VB lanes handled are lanes lo .. lo+VB-1 of VS-lane sample vectors.
-template <typename T, int VB, int MODE, int NQ, int VS = VB, bool ACC = false>
+// dsum_s (BACK_H) holds rho D, scaled when the batch was bound (k_pack_d).
+template <typename T, int VB, int MODE, int NQ, int VS = VB, bool ACC = false, class PSrc = PGlobal>
 __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j, int chunk, int v0, int nv,
-                                              const T (&acc)[VB], double (&pq)[VB][NQ], int lo = 0) {
+                                              const T (&acc)[VB], double (&pq)[VB][NQ], int lo = 0,
+                                              PSrc psrc = PSrc{}) {
   const int N = A.N;
   const int npix = N * N;
   const int pix = i * N + j;
@@ -1442,15 +1462,21 @@ __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j
     T pc[VB], pn[VB], dv[VB], outv[VB];
     F2 kt2[NP > 0 ? NP : 1], pc2[NP > 0 ? NP : 1];
     float kt1 = 0.0f;  // (odd VB: the last lane)
-    gload<T, VB>(pv + (size_t)pix * VS, pc);
+    auto ldp = [&](int ii, int jj, T(&o)[VB]) {
+      if constexpr (std::is_same<PSrc, PGlobal>::value)
+        gload<T, VB>(pv + (size_t)(ii * N + jj) * VS, o);
+      else
+        psrc.load(ii, jj, o);
+    };
+    ldp(i, j, pc);
 #pragma unroll
     for (int h = 0; h < NP; ++h) {
       pc2[h] = F2{pc[2 * h], pc[2 * h + 1]};
       kt2[h] = F2{0.0f, 0.0f};
     }
     // K^T K p in the order of the float64 form: (pc - p_up) - (p_down - pc) + (pc - p_left) - (p_right - pc)
-    auto nb = [&](size_t o, bool sub_pc_first) {
-      gload<T, VB>(pv + o * VS, pn);
+    auto nb = [&](int ii, int jj, bool sub_pc_first) {
+      ldp(ii, jj, pn);
 #pragma unroll
       for (int h = 0; h < NP; ++h) {
         const F2 q = F2{pn[2 * h], pn[2 * h + 1]};
@@ -1458,22 +1484,22 @@ __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j
       }
       if constexpr (VB % 2) kt1 = sub_pc_first ? kt1 + (pc[VB - 1] - pn[VB - 1]) : kt1 - (pn[VB - 1] - pc[VB - 1]);
     };
-    if (i >= 1) nb((size_t)(pix - N), true);
-    if (i <= N - 2) nb((size_t)(pix + N), false);
-    if (j >= 1) nb((size_t)(pix - 1), true);
-    if (j <= N - 2) nb((size_t)(pix + 1), false);
-    gload<T, VB>(A.dsum_s + sbase + (size_t)pix * VS, dv);
-    const float rf = (float)A.rho, mf = (float)A.mu;
-    const F2 rho2 = F2{rf, rf}, mu2 = F2{mf, mf};
+    if (i >= 1) nb(i - 1, j, true);
+    if (i <= N - 2) nb(i + 1, j, false);
+    if (j >= 1) nb(i, j - 1, true);
+    if (j <= N - 2) nb(i, j + 1, false);
+    gload<T, VB>(A.dsum_s + sbase + (size_t)pix * VS, dv);  // (float) D * (float) rho
+    const float mf = (float)A.mu;
+    const F2 mu2 = F2{mf, mf};
 #pragma unroll
     for (int h = 0; h < NP; ++h) {
-      const F2 d2 = F2{dv[2 * h], dv[2 * h + 1]} * rho2;
+      const F2 d2 = F2{dv[2 * h], dv[2 * h + 1]};
       F2 hv = __builtin_elementwise_fma(d2, pc2[h], F2{acc[2 * h], acc[2 * h + 1]});
       hv = __builtin_elementwise_fma(mu2, kt2[h], hv);
       outv[2 * h] = hv.x;
       outv[2 * h + 1] = hv.y;
     }
-    if constexpr (VB % 2) outv[VB - 1] = fmaf(mf, kt1, fmaf(dv[VB - 1] * rf, pc[VB - 1], acc[VB - 1]));
+    if constexpr (VB % 2) outv[VB - 1] = fmaf(mf, kt1, fmaf(dv[VB - 1], pc[VB - 1], acc[VB - 1]));
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
       if (u >= nv) outv[u] = T(0);
@@ -1527,8 +1553,9 @@ __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j
       if (u < nv) {
         const size_t vo = (size_t)(v0 + u) * npix;
         const double pcd = (double)pc[u];
-        const double dd = (MODE == BACK_H) ? (double)dv[u] : A.dsum[vo + pix];
-        const double h = (double)acc[u] + A.rho * dd * pcd + A.mu * ktk[u];
+        // (H: dv is rho D, the product k_pack_d formed -- the same A.rho * D)
+        const double rd = (MODE == BACK_H) ? (double)dv[u] : A.rho * A.dsum[vo + pix];
+        const double h = (double)acc[u] + rd * pcd + A.mu * ktk[u];
         if constexpr (MODE == BACK_H) {
           const T hp = (T)h;
           outv[u] = hp;
@@ -2023,7 +2050,51 @@ template <typename T, int VB, int MODE>
 constexpr bool back_mirror_dma() {
   return ADMM_BK_DMA && MODE == BACK_H && Planes<T, VB>::NPL == 2 && sizeof(Pack<T, Planes<T, VB>::PV>) == 16;
 }
-template <typename T, int VB, int VBR, int MODE, bool DMAQ>
+// The H epilogue's p stencil from LDS (float32, LDS-DMA kernels; ADMM_BK_EPI=global at context
+// creation keeps the global loads: A/B and the bitwise test).  Per-pixel global loads fetch every
+// p vector of a tile five times through the vector L1, by five threads, in the burst that also
+// streams D, r and Hp.  Instead, after the last chunk's taps -- when the window LDS holds nothing
+// -- the block stages per lane block the p tile of its upper rows ib-1 .. ib+kBTI and of the
+// mirrored rows N-1-ib-kBTI .. N-ib, each with a one-pixel halo ((kBTI+2) x (kBTJ+2) 16-byte
+// slots, a pixel's MH samples), into the window array by LDS-DMA, and the epilogue takes the
+// pixel and its four neighbours from there (PTile).  Slots off the image are out-of-range
+// offsets (zero-filled, and never read: the stencil's edge guards).  Not overlapped with the
+// taps: that variant lost to the clock.
+constexpr int kPtR = kBTI + 2, kPtC = kBTJ + 2, kPtSlots = kPtR * kPtC;
+using lds_char = __attribute__((address_space(3))) char;
+template <int LB>
+constexpr int ptile_bytes() {  // whole 64-slot DMA pieces
+  return ((2 * LB * kPtSlots + 63) / 64) * 64 * 16;
+}
+// tile (l, half) of lane block z0 + l at byte (2 l + half) x kPtSlots x 16 of lds; the caller
+// waits for the DMA (vmcnt(0), then a barrier) before any wave reads it
+template <typename T, int VBR, int MH, int LB>
+__device__ __forceinline__ void ptile_stage(const BackArgs<T>& A, lds_char* lds, int ib, int jb, int z0) {
+  static_assert(MH * sizeof(T) == 16, "one 16-byte slot per pixel and lane block");
+  constexpr int MS = VBR / MH, NSLOT = 2 * LB * kPtSlots, NPC = (NSLOT + 63) / 64;
+  const int N = A.N, npix = N * N;
+  const int lane = threadIdx.x & 63;
+  const int wvu = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const uint64_t b = (uint64_t)(uintptr_t)A.pin;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+  const __amdgpu_buffer_rsrc_t rs =  // every chunk of p: the lane blocks differ in their offsets only
+      make_rsrc((const void*)(uintptr_t)(((uint64_t)hi << 32) | lo),
+                (uint32_t)((size_t)((A.V + VBR - 1) / VBR) * npix * VBR * sizeof(T)));
+  for (int pc = wvu; pc < NPC; pc += kBkWaves) {  // (wave-uniform)
+    const int q = pc * 64 + lane;
+    const int t = q / kPtSlots, s = q - t * kPtSlots, rr = s / kPtC, cc = s - rr * kPtC;
+    const int z = z0 + (t >> 1);
+    const int row = ((t & 1) ? N - 1 - ib - kBTI : ib - 1) + rr, col = jb - 1 + cc;
+    const bool in = q < NSLOT && row >= 0 && row < N && col >= 0 && col < N;
+    const unsigned voff =
+        in ? (unsigned)(((z / MS) * npix + row * N + col) * VBR + (z % MS) * MH) * (unsigned)sizeof(T) : 0xFFFFFFFFu;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(lds + pc * (64 * 16)), 16,
+                                             voff, 0, 0, 0);
+  }
+}
+
+template <typename T, int VB, int VBR, int MODE, bool DMAQ, bool EPIQ = true>
 __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   static_assert(MODE == BACK_H || MODE == BACK_INIT || MODE == BACK_DIAG || MODE == BACK_ATB, "batch modes");
   constexpr int MH = VB / 2, MS = VBR / MH;
@@ -2067,6 +2138,9 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   constexpr bool DMA = DMAQ && back_mirror_dma<T, VB, MODE>();
   constexpr int NWB = DMA ? 4 : 2, NKS = DMA ? 3 : 2;
   constexpr int BUFB = 2 * NPL * ANGC * kBWin * PB;  // bytes of one chunk's windows
+  // the H epilogue's p stencil from a tile staged in win after the taps (ptile_stage)
+  constexpr bool EPI = EPIQ && DMA && std::is_same<T, float>::value && MH * sizeof(T) == 16;
+  static_assert(!EPI || ptile_bytes<1>() <= 2 * BUFB, "the p tiles fit in the window array");
   __shared__ Pack<T, PV> win[NWB][NPL][ANGC][kBWin];  // [buffer x 2 + window (upper / mirror tile)]
   __shared__ int4 kmin_s[NKS][2][ANGC / 4 + 1];       // [slot][window]: byte offsets koff
   __shared__ int kst_s[DMA ? 3 : 1][2][DMA ? ANGC + 1 : 1];  // DMA: [slot][window] first bin - kbias
@@ -2335,6 +2409,17 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
     __shared__ double diag_s[kDiagScratch];
     diag_epilogue_tile<T, MH, VBR>(A, diag_s, ib, jb, i, j, inb, rc, v0, nv, r1, pq, mq * MH);
     diag_epilogue_tile<T, MH, VBR>(A, diag_s, N - ib - kBTI, jb, i2, j, inb2, rc, v0, nv, r2, pq, mq * MH);
+  } else if constexpr (EPI) {
+    lds_char* const tb = (lds_char*)&win[0][0][0][0];
+    __syncthreads();  // no wave still reads the last chunk's windows
+    ptile_stage<T, VBR, MH, 1>(A, tb, ib, jb, chunk);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces landed ...
+    __syncthreads();                                  // ... and every other wave's
+    using PT = PTile<T, MH, kPtC>;
+    if (inb) back_epilogue<T, MH, MODE, NQ, VBR, false, PT>(A, i, j, rc, v0, nv, r1, pq, mq * MH, PT{tb, ib - 1, jb - 1});
+    if (inb2)
+      back_epilogue<T, MH, MODE, NQ, VBR, true, PT>(A, i2, j, rc, v0, nv, r2, pq, mq * MH,
+                                                    PT{tb + kPtSlots * 16, N - 1 - ib - kBTI, jb - 1});
   } else {
     if (inb) back_epilogue<T, MH, MODE, NQ, VBR>(A, i, j, rc, v0, nv, r1, pq, mq * MH);
     if (inb2) back_epilogue<T, MH, MODE, NQ, VBR, true>(A, i2, j, rc, v0, nv, r2, pq, mq * MH);
@@ -2368,6 +2453,11 @@ template <typename T, int VB, int VBR, int MODE>
 __global__ __launch_bounds__(kBkThreads) void k_back_mirror_reg(BackArgs<T> A) {
   back_mirror_body<T, VB, VBR, MODE, false>(A);
 }
+// LDS-DMA windows, the H epilogue's p stencil by global loads (ADMM_BK_EPI=global)
+template <typename T, int VB, int VBR, int MODE>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror_gepi(BackArgs<T> A) {
+  back_mirror_body<T, VB, VBR, MODE, true, false>(A);
+}
 
 // ===========================================================================
 // Mirror back projector, H mode, two lane blocks per block (round 6, `ADMM_BK_LB2`): the same
@@ -2377,9 +2467,11 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_reg(BackArgs<T> A) {
 // k_back_mirror's DMA path (half the angles per chunk: the two lane blocks' windows in two
 // buffers fill the same 98 KB), and the grid is half as many blocks.  Per lane block the
 // arithmetic is k_back_mirror's in the same order: bitwise the same Hp and dot partials.
+// After the taps the four p tiles (two lane blocks x upper / mirrored rows, 74 KB) are staged
+// into the window array and the epilogues read their p stencil there (ptile_stage).
 // ===========================================================================
-template <typename T, int VB, int VBR>
-__global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
+template <typename T, int VB, int VBR, bool EPI>  // EPI: the p stencil from LDS (ptile_stage)
+__device__ __forceinline__ void back_mirror_2_body(const BackArgs<T>& A) {
   constexpr int MODE = BACK_H, NQ = 5, LB = 2;
   constexpr int MH = VB / 2, MS = VBR / MH;
   static_assert(VB % 2 == 0 && VBR % MH == 0, "mirror: VB = 2 x (a divisor of VBR)");
@@ -2406,6 +2498,7 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
   static_assert(ANGC % 4 == 0 && ANGC >= 4, "angle chunks are read as int4 groups");
   constexpr int WINB = 2 * NPL * ANGC * kBWin * PB;  // bytes of one lane block's windows per chunk
   constexpr int BUFB = LB * WINB;                    // bytes of one chunk buffer
+  static_assert(!EPI || (MH * sizeof(T) == 16 && ptile_bytes<LB>() <= 2 * BUFB), "the p tiles fit in the window array");
   __shared__ Pack<T, PV> win[2 * LB * 2][NPL][ANGC][kBWin];  // [buffer][lane block][window]
   __shared__ int4 kmin_s[3][2][ANGC / 4 + 1];                // [slot][window]: byte offsets koff
   __shared__ int kst_s[3][2][ANGC + 1];                      // [slot][window]: first bin - kbias
@@ -2541,6 +2634,13 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
   __shared__ double tot[NS];
   const int P = gridDim.x * gridDim.y;
   const int b = blockIdx.y * gridDim.x + blockIdx.x;
+  lds_char* const tb = (lds_char*)&win[0][0][0][0];
+  if constexpr (EPI) {
+    __syncthreads();  // no wave still reads the last chunk's windows
+    ptile_stage<T, VBR, MH, LB>(A, tb, ib, jb, (int)blockIdx.z * LB);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces landed ...
+    __syncthreads();                                  // ... and every other wave's
+  }
 #pragma unroll
   for (int l = 0; l < LB; ++l) {
     if (A.wexp != 0) {
@@ -2563,8 +2663,18 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
       for (int q = 0; q < NQ; ++q) pq[u][q] = 0.0;
     const int z = (int)blockIdx.z * LB + l, rc = z / MS, mq = z % MS;
     const int v0 = rc * VBR + mq * MH, nv = min(MH, A.V - v0);
-    if (inb) back_epilogue<T, MH, MODE, NQ, VBR>(A, i, j, rc, v0, nv, r1, pq, mq * MH);
-    if (inb2) back_epilogue<T, MH, MODE, NQ, VBR, true>(A, i2, j, rc, v0, nv, r2, pq, mq * MH);
+    if constexpr (EPI) {
+      using PT = PTile<T, MH, kPtC>;
+      if (inb)
+        back_epilogue<T, MH, MODE, NQ, VBR, false, PT>(A, i, j, rc, v0, nv, r1, pq, mq * MH,
+                                                       PT{tb + (2 * l) * kPtSlots * 16, ib - 1, jb - 1});
+      if (inb2)
+        back_epilogue<T, MH, MODE, NQ, VBR, true, PT>(A, i2, j, rc, v0, nv, r2, pq, mq * MH,
+                                                      PT{tb + (2 * l + 1) * kPtSlots * 16, N - 1 - ib - kBTI, jb - 1});
+    } else {
+      if (inb) back_epilogue<T, MH, MODE, NQ, VBR>(A, i, j, rc, v0, nv, r1, pq, mq * MH);
+      if (inb2) back_epilogue<T, MH, MODE, NQ, VBR, true>(A, i2, j, rc, v0, nv, r2, pq, mq * MH);
+    }
     double flat[NT];
 #pragma unroll
     for (int u = 0; u < MH; ++u)
@@ -2574,6 +2684,15 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
     const int t = threadIdx.x;
     if (t < NT && t / NQ < nv) A.part[((size_t)v0 * NQ + t) * P + b] = tot[t];
   }
+}
+template <typename T, int VB, int VBR>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
+  back_mirror_2_body<T, VB, VBR, true>(A);
+}
+// the H epilogue's p stencil by global loads (ADMM_BK_EPI=global)
+template <typename T, int VB, int VBR>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror_2_gepi(BackArgs<T> A) {
+  back_mirror_2_body<T, VB, VBR, false>(A);
 }
 
 // ===========================================================================
@@ -2620,6 +2739,13 @@ __device__ __forceinline__ void tile_store_T(TileT<T, VB>& tl, T* __restrict__ o
 // (BACK_INIT's epilogue with its projected A^T A xs replaced; xs and its four neighbours
 // are (T) x read straight from x), p also written transposed.  One thread per pixel, all
 // VB nodes of the chunk; a block is kTile x kCgRows pixels (the CG update's grid).
+// ADMM_SR_LDS: the block stages (T) x of its tile plus a one-pixel halo per node in LDS once
+// (the tile's 32 aligned columns of every row first, then the two halo columns) and the
+// stencil reads it there -- 2 float64 loads per thread and node instead of 5, the same casts
+// in the same order.
+#ifndef ADMM_SR_LDS
+#define ADMM_SR_LDS 1
+#endif
 template <typename T, int VB>
 __global__ __launch_bounds__(kBlock) void k_start_reuse(
     const T* __restrict__ ats, const double* __restrict__ x, EdgeIn E, const double* __restrict__ q,
@@ -2635,6 +2761,35 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
   const int jj = threadIdx.x % kTile, ii = threadIdx.x / kTile;
   const int i0 = blockIdx.y * ROWS, j0 = blockIdx.x * kTile;
   const int i = i0 + ii, j = j0 + jj;
+#if ADMM_SR_LDS
+  __shared__ T xt[VB][ROWS + 2][kTile + 2];  // (T) x over rows i0 - 1 .., columns j0 - 1 ..; 0 off the image
+  {
+    constexpr int NIN = (ROWS + 2) * kTile, NEL = (ROWS + 2) * (kTile + 2);
+    constexpr int PER = (NEL + kBlock - 1) / kBlock;
+    double xl[VB][PER];
+#pragma unroll
+    for (int u = 0; u < VB; ++u)
+#pragma unroll
+      for (int e = 0; e < PER; ++e) {
+        const int q = (int)threadIdx.x + e * kBlock;
+        const int rr = q < NIN ? q / kTile : (q - NIN) >> 1;
+        const int cc = q < NIN ? 1 + q % kTile : ((q - NIN) & 1) * (kTile + 1);
+        const int row = i0 - 1 + rr, col = j0 - 1 + cc;
+        const bool in = q < NEL && u < nv && row >= 0 && row < N && col >= 0 && col < N;
+        xl[u][e] = in ? x[(size_t)(v0 + u) * npix + row * N + col] : 0.0;
+      }
+#pragma unroll
+    for (int u = 0; u < VB; ++u)
+#pragma unroll
+      for (int e = 0; e < PER; ++e) {
+        const int q = (int)threadIdx.x + e * kBlock;
+        const int rr = q < NIN ? q / kTile : (q - NIN) >> 1;
+        const int cc = q < NIN ? 1 + q % kTile : ((q - NIN) & 1) * (kTile + 1);
+        if (q < NEL) xt[u][rr][cc] = (T)xl[u][e];
+      }
+    __syncthreads();
+  }
+#endif
   if (i < N && j < N) {
     const int pix = i * N + j;
     T av[VB], outv[VB];
@@ -2645,7 +2800,6 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
       if (u < nv) {
         const int v = v0 + u;
         const size_t vo = (size_t)v * npix;
-        const double* xv = x + vo;
         double cc = 0.0;
         for (int qq = inc_off[v]; qq < inc_off[v + 1]; ++qq) {
           const double vij = edge_v(E, inc_edge[qq], inc_sign[qq], npix, pix);
@@ -2653,12 +2807,22 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
         }
         cvec[vo + pix] = cc;
         // K^T K xs at (i, j) from (T) x, in BACK_INIT's order
+#if ADMM_SR_LDS
+        const double pcd = (double)xt[u][ii + 1][jj + 1];
+        double ktk = 0.0;
+        if (i >= 1) ktk += pcd - (double)xt[u][ii][jj + 1];
+        if (i <= N - 2) ktk -= (double)xt[u][ii + 2][jj + 1] - pcd;
+        if (j >= 1) ktk += pcd - (double)xt[u][ii + 1][jj];
+        if (j <= N - 2) ktk -= (double)xt[u][ii + 1][jj + 2] - pcd;
+#else
+        const double* xv = x + vo;
         const double pcd = (double)(T)xv[pix];
         double ktk = 0.0;
         if (i >= 1) ktk += pcd - (double)(T)xv[pix - N];
         if (i <= N - 2) ktk -= (double)(T)xv[pix + N] - pcd;
         if (j >= 1) ktk += pcd - (double)(T)xv[pix - 1];
         if (j <= N - 2) ktk -= (double)(T)xv[pix + 1] - pcd;
+#endif
         const double ab = atb[vo + pix];
         const double h = ((double)av[u] + ab) + rho * dsum[vo + pix] * pcd + mu * ktk;
         const double rr = ab + rho * cc + mu * kt_w_at(dvar + 2 * vo, evar + 2 * vo, N, i, j) - h;
@@ -3103,15 +3267,18 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
   tv_tile_store_T<T, VB>(tl, pT + sbase, N, i0, j0);
 }
 
-// node-major float64 [V][L] -> interleaved samples [C][L][VB] of type T  (grid.y = chunk)
+// node-major float64 [V][L] -> interleaved samples [C][L][VB] of type T, times scale in T: the
+// BACK_H epilogue's rho D, the product (T) D * (T) rho it formed per pixel and launch when D was
+// packed unscaled  (grid.y = chunk)
 template <typename T, int VB>
-__global__ void k_pack_d(const double* __restrict__ in, T* __restrict__ out, int L, int V) {
+__global__ void k_pack_d(const double* __restrict__ in, T* __restrict__ out, int L, int V, double scale) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   const int chunk = blockIdx.y, v0 = chunk * VB;
   if (q >= L) return;
+  const T sc = (T)scale;
   T s[VB];
 #pragma unroll
-  for (int u = 0; u < VB; ++u) s[u] = (v0 + u < V) ? (T)in[(size_t)(v0 + u) * L + q] : T(0);
+  for (int u = 0; u < VB; ++u) s[u] = (v0 + u < V) ? (T)in[(size_t)(v0 + u) * L + q] * sc : T(0);
   gstore<T, VB>(out + ((size_t)chunk * L + q) * VB, s);
 }
 
