@@ -1500,12 +1500,19 @@ __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j
       outv[2 * h + 1] = hv.y;
     }
     if constexpr (VB % 2) outv[VB - 1] = fmaf(mf, kt1, fmaf(dv[VB - 1], pc[VB - 1], acc[VB - 1]));
+    // r of the pixel's live lanes (float64, node-major: one 8-byte load per lane), all issued
+    // together ahead of the dots so that they are in flight at once (with one load inside each
+    // lane's dots k_back_mirror_2 ran 51.2 us at C3, so 49.1; issued before the p stencil
+    // instead: the same 49.1; profiles/AB_LOG.md round 8)
+    double rl[VB];
+#pragma unroll
+    for (int u = 0; u < VB; ++u) rl[u] = u < nv ? A.r[(size_t)(v0 + u) * npix + pix] : 0.0;
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
       if (u >= nv) outv[u] = T(0);
       if (u < nv) {
         const double hd = (double)outv[u], pcd = (double)pc[u];
-        const double rv = A.r[(size_t)(v0 + u) * npix + pix];
+        const double rv = rl[u];
         pq[u][0] = fma(pcd, hd, ACC ? pq[u][0] : 0.0);
         pq[u][1] = fma(rv, hd, ACC ? pq[u][1] : 0.0);
         pq[u][2] = fma(hd, hd, ACC ? pq[u][2] : 0.0);
