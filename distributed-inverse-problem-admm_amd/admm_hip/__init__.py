@@ -8,6 +8,7 @@ The reference-compatible entry points are the drop-in modules one directory up
 from .geometry import ParallelBeamGeometry, RayTransform, split_angles  # noqa: F401
 from ._lib import AdmmError, AdmmLibraryError  # noqa: F401
 from .fbp import FILTERS, fbp, filter_taps, ramp_filter  # noqa: F401
+from .metrics import image_metrics, psnr, ssim  # noqa: F401
 
 __all__ = ["ParallelBeamGeometry", "RayTransform", "split_angles", "AdmmError", "AdmmLibraryError",
-           "FILTERS", "fbp", "filter_taps", "ramp_filter"]
+           "FILTERS", "fbp", "filter_taps", "ramp_filter", "image_metrics", "psnr", "ssim"]

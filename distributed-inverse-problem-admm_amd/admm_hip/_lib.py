@@ -31,6 +31,7 @@ ADMM_FBP_RAMLAK = 0
 ADMM_FBP_SHEPP_LOGAN = 1
 ADMM_FBP_HANN = 2
 FBP_MAX_DET = 4096
+METRICS_MIN_N, METRICS_MAX_N = 11, 4096  # admm_image_metrics: one 11 x 11 window .. the library's limit
 NODE_STATS = 6  # mse_sino, |g|^2, TV, quad, img, split-Bregman stationarity residual^2
 EDGE_STATS = 3  # |x_a-z|^2, |x_b-z|^2, |dz|^2
 
@@ -123,6 +124,9 @@ SYMBOLS = {
                           C.POINTER(C.c_uint64)],
     "admm_fbp_filter": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                         C.c_int, C.c_void_p],
+    "admm_image_metrics": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                           C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_image_metrics_work": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
 }
 
 _lock = threading.Lock()

@@ -42,7 +42,9 @@ from .exchange import split_stats
 from .fbp import FILTERS, fbp
 from .geometry import RayTransform
 from .groups import RankGroups
+from ._lib import NODE_STATS as _NODE_STATS
 from .matrix import MatrixOperator, as_operators
+from .metrics import check_data_range, check_metrics, check_side, _check_mask_shape
 
 HISTORY_KEYS = (
     "primal", "dual", "pri_per_node", "dual_per_node", "obj_per_node", "obj_total",
@@ -88,8 +90,17 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              cg_iters=5, tv_kind="iso", group=None, return_tensors=False, timing=None,
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
-             pipeline=None, streams=1, edge_state=None, x_init=None):
-    """``x_init``: where the run starts.  None: x = 0, z = 0 (the reference, _ver2:35-43).
+             pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
+             metrics_mask=None):
+    """``metrics``: None, or a subset of ("psnr", "ssim"): after every iteration's x-update each
+    node's image is scored against ``phantom_true`` (required then) on the GPU (admm_hip.metrics,
+    admm_image_metrics on the batch's stream) and the history gains ``psnr_per_node`` / ``psnr_mean``
+    and / or ``ssim_per_node`` / ``ssim_mean`` (one V_total array / its mean per iteration); the
+    values ride in extra columns of the node-statistics table, so the pipelined mode stays free of
+    host synchronisation.  ``data_range``: L of both (default phantom.max() - phantom.min(), > 0);
+    ``metrics_mask``: (N, N) or (n,), nonzero = pixel counted (default all).  With ``metrics=None``
+    nothing changes: no launch, no table column, no history key.
+    ``x_init``: where the run starts.  None: x = 0, z = 0 (the reference, _ver2:35-43).
     "fbp" or "fbp:<filter>" (admm_hip.fbp.FILTERS): node g starts from the filtered back
     projection of its own sinogram, ``A_g.fbp(sinograms[g], filter)``.  A list, array or tensor of
     one image per graph node, (N, N) or (n,): node g starts from entry g (converted to float64).
@@ -118,6 +129,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         if inner_tol is not None:
             raise ValueError("inner_chunks and inner_tol are exclusive")
         tv_iters = inner_chunks[0]
+    # argument errors on every rank alike, before any operator is built on the device
+    metrics = _check_metric_args(metrics, data_range, metrics_mask, phantom_true, N)
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through
@@ -143,9 +156,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     plan = rg.plan
     if start is not None:
         rg.start_from(_initial_images(start, A_dense_list, sinograms, plan.local_nodes, rg.device))
+    if metrics:
+        rg.enable_metrics(metrics, data_range, metrics_mask)
     if world > 1:
         dist.barrier(group=group)
     hist = {k: [] for k in HISTORY_KEYS + EXTRA_KEYS}
+    for name in metrics or ():
+        hist[f"{name}_per_node"], hist[f"{name}_mean"] = [], []
     edges = plan.edges
     have_ph = phantom_true is not None
     if verbose and rank == 0:
@@ -181,6 +198,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             for nb in rg.batches:
                 rows = [plan.local_nodes.index(g) for g in nb.plan.local_nodes]
                 eps_used[rows], n_upd[rows] = _solve_to_reference_tolerance(nb, et, max_inner_updates)
+        if metrics:
+            rg.score_images()  # x is final for this iteration: the consensus writes z and y only
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
         iters_done = k + 1
         if pipelined:
@@ -191,10 +210,11 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             dev_hist[k - flushed].copy_(flat)
             if k + 1 - flushed == dev_hist.shape[0]:  # block full: flush to the host
                 flushed = _flush_pipelined(hist, dev_hist, flushed, k + 1, rg, V_total, edges, rho, lam_tv,
-                                           have_ph, verbose and rank == 0)
+                                           have_ph, verbose and rank == 0, metrics)
             continue
         ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))
-        pn, dn = _record(hist, ns.numpy(), es.numpy(), edges, V_total, rho, lam_tv, et, have_ph)
+        pn, dn = _record(hist, _take_metrics(hist, metrics, ns.numpy()), es.numpy(), edges, V_total, rho, lam_tv,
+                         et, have_ph)
         if snapshot_dir is not None and ((k + 1) % snapshot_every == 0):
             _snapshot(snapshot_dir, k, rg, N)
         if verbose and rank == 0 and k % 10 == 0:
@@ -205,7 +225,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             break
     if pipelined and dev_hist is not None and iters_done > flushed:
         flushed = _flush_pipelined(hist, dev_hist, flushed, iters_done, rg, V_total, edges, rho, lam_tv, have_ph,
-                                   verbose and rank == 0)
+                                   verbose and rank == 0, metrics)
     torch.cuda.synchronize()
     if timing is not None:
         import time
@@ -269,16 +289,45 @@ def _initial_images(start, A_list, sinograms, local_nodes, dev):
     return out
 
 
-def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose):
+def _check_metric_args(metrics, data_range, metrics_mask, phantom_true, N):
+    """Validate run_admm's metric keywords without device work; the requested names or None."""
+    metrics = check_metrics(metrics)
+    if metrics is None:
+        if data_range is not None or metrics_mask is not None:
+            raise ValueError("data_range / metrics_mask need metrics=('psnr', 'ssim') or a subset")
+        return None
+    if phantom_true is None:
+        raise ValueError(f"metrics={metrics!r} needs phantom_true: PSNR and SSIM are taken against it")
+    check_side(N)
+    check_data_range(data_range)
+    if metrics_mask is not None:
+        _check_mask_shape(metrics_mask, N)
+    return metrics
+
+
+def _take_metrics(hist, metrics, ns):
+    """Record the metric columns (right after the library's node statistics) of one iteration's
+    node table and return the table without them -- the table of a run without metrics."""
+    if not metrics:
+        return ns
+    c0, c1 = _NODE_STATS, _NODE_STATS + len(metrics)
+    for j, name in enumerate(metrics):
+        col = ns[:, c0 + j].copy()
+        hist[f"{name}_per_node"].append(col)
+        hist[f"{name}_mean"].append(float(np.mean(col)))
+    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1)
+
+
+def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None):
     """Record iterations k0 .. k1-1 of the pipelined statistics (rows 0 .. k1-k0-1 of
     ``dev_hist``) on the host; returns k1."""
     host = dev_hist[: k1 - k0].to("cpu")
-    nsw = rg.batches[0].node_stats.shape[1]
+    nsw = rg.batches[0].node_stats.shape[1] + len(metrics or ())
     extra = np.stack([np.full(V_total, np.nan), np.ones(V_total)], axis=1)
     for k in range(k0, k1):
         ns, es = split_stats(host[k - k0], V_total, nsw, len(edges), rg.batches[0].edge_stats.shape[1])
-        pn, dn = _record(hist, np.concatenate([ns.numpy(), extra], axis=1), es.numpy(), edges, V_total,
-                         rho, lam_tv, eps_target(k), have_ph)
+        pn, dn = _record(hist, np.concatenate([_take_metrics(hist, metrics, ns.numpy()), extra], axis=1), es.numpy(),
+                         edges, V_total, rho, lam_tv, eps_target(k), have_ph)
         if verbose and k % 10 == 0:
             print(f"iter {k}, primal {pn:.3e}, dual {dn:.3e}")
     return k1

@@ -166,6 +166,7 @@ class RankGroups:
                               f"stream", RuntimeWarning)
                 streams = 1
         self.streams_requested = streams
+        self.metric_names = ()  # enable_metrics
         bs = rank_batches(A_list, self.plan, streams)
         keys = [k for k, _ in bs]
         members = dict(bs)
@@ -286,12 +287,35 @@ class RankGroups:
         self.halo.finish(h)
         nb.consensus_range(nb.plan.n_internal, len(nb.plan.stored_edges), nb.plan.n_xext)
 
+    def enable_metrics(self, names, data_range=None, mask=None) -> None:
+        """Score every batch's images against its phantom from now on (metrics.Scorer, one per
+        batch: each owns its kernel scratch, so concurrent batches do not share any).  Every rank
+        and batch derives the same L and pixel counts from the same phantom and mask."""
+        from .metrics import Scorer
+        self.metric_names = tuple(names)
+        for nb in self.batches:
+            nb.scorer = Scorer(nb.phantom, data_range, mask, device=nb.device, max_images=nb.V)
+            nb.metric_cols = None
+
+    def score_images(self) -> None:
+        """Each batch's ``metric_cols`` <- the requested metrics of its current local images,
+        (V, k) on the device, on the batch's stream."""
+        def score(nb):
+            nb.metric_cols = nb.scorer.columns(nb.x_local, self.metric_names)
+        self._concurrent(score)
+
+    def _node_stats(self, nb):
+        """The batch's node-statistics rows, widened by its metric columns when metrics are on."""
+        if self.metric_names:
+            return torch.cat([nb.node_stats, nb.metric_cols], 1)
+        return nb.node_stats
+
     def stats(self, extra=None):
         """Global node / edge statistics; ``extra`` (rank-local [V, k] numpy, rows in
         plan.local_nodes order) is appended to the node statistics."""
         parts = []
         for nb in self.batches:
-            ns = nb.node_stats
+            ns = self._node_stats(nb)
             if extra is not None:
                 rows = [self.plan.local_nodes.index(g) for g in nb.plan.local_nodes]
                 ex = torch.as_tensor(extra[rows], dtype=torch.float64, device=ns.device)
@@ -302,7 +326,7 @@ class RankGroups:
     def stats_device(self) -> torch.Tensor:
         """The global statistics table on the device (exchange.assemble_stats_device): no
         host synchronisation."""
-        parts = [(nb.plan, nb.node_stats, nb.edge_stats[: len(nb.plan.stored_edges)]) for nb in self.batches]
+        parts = [(nb.plan, self._node_stats(nb), nb.edge_stats[: len(nb.plan.stored_edges)]) for nb in self.batches]
         return assemble_stats_device(self.plan.V_total, len(self.plan.edges), self.world, parts, self.group)
 
     def local_images(self):

@@ -21,6 +21,11 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 "fbp:<filter>" (node g starts from the filtered back projection of its own
                 sinogram, admm_hip/fbp.py) or one image per graph node ((N, N) or (n,)); the
                 run is then a fresh ADMM around those images (y = 0, z = edge means)
+* ``metrics``   None (default) or a subset of ("psnr", "ssim"): per-node image quality against
+                ``phantom_true`` after every iteration, computed on the GPU (admm_hip/metrics.py);
+                adds the history keys psnr_per_node / psnr_mean, ssim_per_node / ssim_mean
+* ``data_range``    L of PSNR and SSIM (default phantom_true.max() - phantom_true.min())
+* ``metrics_mask``  (N, N) or (n,) mask of the pixels the metrics count (default: all)
 
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
@@ -37,7 +42,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        snapshot_every=None, snapshot_div=10, phantom_true=None,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
-                       max_inner_updates=10, x_init=None):
+                       max_inner_updates=10, x_init=None, metrics=None, data_range=None,
+                       metrics_mask=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
     del max_inner_iters  # accepted but unused, as in the reference (_ver2:17)
     return run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=lam_tv, rho=rho,
@@ -46,4 +52,5 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     snapshot_div=snapshot_div, phantom_true=phantom_true, mu=mu,
                     tv_iters=tv_iters, cg_iters=cg_iters, tv_kind=tv_kind, group=group,
                     write_params=write_params, fusion=fusion, inner_tol=inner_tol,
-                    max_inner_updates=max_inner_updates, x_init=x_init)
+                    max_inner_updates=max_inner_updates, x_init=x_init, metrics=metrics,
+                    data_range=data_range, metrics_mask=metrics_mask)

@@ -292,6 +292,30 @@ int admm_chain_orders(const uint64_t pcg[4], int has_uint32, uint32_t uinteger, 
 int admm_fbp_filter(const void* sino, void* out, int dtype, int n_angles, int n_det, int nimg,
                     double det_spacing, double scale, int filter, void* stream);
 
+/* --- image quality of the reconstructions: squared error and SSIM sums --- */
+
+/* out[v][0] = sum_p (img_v[p] - ref[p])^2 over the pixels with mask[p] != 0 (mask NULL: all N * N) and
+ * out[v][1] = the sum of the SSIM map of (img_v, ref) over the valid window centres 5 <= i, j <= N - 6
+ * under the same mask, for v < nimg; img_v = img + v * img_stride (doubles, img_stride >= N * N), ref one
+ * [N * N] image, mask [N * N] uint8 or NULL, out [nimg][2]: float64 device pointers, C-order pixels.
+ * The squared error is what the reference's evaluation helper scores strategies by
+ * (test_final_integration.py:41-50: psnr = 20 log10(data_range) - 10 log10(mean((x_hat - x_true)^2)) with
+ * data_range = x_true.max() - x_true.min(), then the mean over nodes); the caller divides by its pixel
+ * counts (admm_hip/metrics.py).  SSIM as Wang et al. 2004: 11 x 11 Gaussian window, sigma = 1.5,
+ * normalised to sum 1; moments mx, my, E[x^2], E[y^2], E[xy], population (co)variances E[.] - mu mu,
+ * S = (2 mx my + c1)(2 sxy + c2) / ((mx^2 + my^2 + c1)(sx^2 + sy^2 + c2)), c1 = (0.01 L)^2,
+ * c2 = (0.03 L)^2 for data range L; no boundary extension.  All arithmetic float64 with explicit fma; no
+ * atomics: per-tile partial sums in fixed slots of `work`, then one fixed-order sum per image, so an
+ * image's two outputs depend neither on nimg, nor on its place in the batch, nor on img_stride.
+ * Masked-out pixels and centres contribute exactly 0 whatever they hold.  `work`: caller-owned scratch of
+ * admm_image_metrics_work doubles; nothing is allocated.  Context-free like admm_fbp_filter;
+ * 11 <= N <= 4096, 1 <= nimg <= 65535, c1, c2 > 0.  Asynchronous on `stream` (current device).
+ * Additive: ADMM_ABI_VERSION stays 9. */
+int admm_image_metrics(const double* img, long long img_stride, const double* ref, const uint8_t* mask,
+                       int N, int nimg, double c1, double c2, double* work, double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_image_metrics needs for this N and nimg.  No device work. */
+int admm_image_metrics_work(int N, int nimg, long long* n_doubles);
+
 #ifdef __cplusplus
 }
 #endif
