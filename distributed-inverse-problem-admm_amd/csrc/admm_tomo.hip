@@ -534,32 +534,23 @@ int launch_back(admm_ctx* C, BackArgs<T> a, int V, hipStream_t s) {
       a.V = V;
       const int N = C->g.N, Nh = (N + 1) / 2;
       dim3 grid((N + kBTJ - 1) / kBTJ, (Nh + kBTI - 1) / kBTI, ((V + VB - 1) / VB) * (VB / MH));
-      bool done = false;
+      void (*kern)(BackArgs<T>) = k_back_mirror<T, VBV, VB, MODE>;
       if constexpr (back_mirror_dma<T, VBV, MODE>()) {
-        if (C->bk_staging == 1) {  // the register-staged windows (where DMA is the default)
-          hipLaunchKernelGGL((k_back_mirror_reg<T, VBV, VB, MODE>), grid, dim3(kBkThreads), 0, s, a);
-          done = true;
-        } else if constexpr (std::is_same<T, float>::value && ADMM_BK_LB2) {
+        // the variants where LDS-DMA is the default (bk_staging: 0 default, 1 reg, 2 dma1, 3 dma2)
+        if (C->bk_staging == 1) {
+          kern = k_back_mirror_reg<T, VBV, VB, MODE>;
+        } else if constexpr (std::is_same<T, float>::value) {
           // two lane blocks per block while half the blocks still give every CU one
           const bool fills = (long)grid.x * grid.y * grid.z >= 2L * C->n_cu;
           if (grid.z % 2 == 0 && (C->bk_staging == 3 || (C->bk_staging == 0 && fills))) {
-            if (C->bk_epi_lds)
-              hipLaunchKernelGGL((k_back_mirror_2<T, VBV, VB>), dim3(grid.x, grid.y, grid.z / 2),
-                                 dim3(kBkThreads), 0, s, a);
-            else
-              hipLaunchKernelGGL((k_back_mirror_2_gepi<T, VBV, VB>), dim3(grid.x, grid.y, grid.z / 2),
-                                 dim3(kBkThreads), 0, s, a);
-            done = true;
-          }
-        }
-        if constexpr (std::is_same<T, float>::value) {
-          if (!done && !C->bk_epi_lds) {
-            hipLaunchKernelGGL((k_back_mirror_gepi<T, VBV, VB, MODE>), grid, dim3(kBkThreads), 0, s, a);
-            done = true;
+            kern = C->bk_epi_lds ? k_back_mirror_2<T, VBV, VB> : k_back_mirror_2_gepi<T, VBV, VB>;
+            grid.z /= 2;
+          } else if (!C->bk_epi_lds) {
+            kern = k_back_mirror_gepi<T, VBV, VB, MODE>;
           }
         }
       }
-      if (!done) hipLaunchKernelGGL((k_back_mirror<T, VBV, VB, MODE>), grid, dim3(kBkThreads), 0, s, a);
+      hipLaunchKernelGGL(kern, grid, dim3(kBkThreads), 0, s, a);
       CHECK_LAUNCH();
       return ADMM_OK;
     }

@@ -86,6 +86,51 @@ __device__ __forceinline__ int kf_addr(unsigned hi, int koff) {
   asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(off) : "v"(hi), "i"(SH), "v"(koff));
   return off;
 }
+// One float32 tap of the back projectors from the biased position kfb: the weights w0, w1 of bins
+// floor(k_f), floor(k_f) + 1 and the LDS byte offset of the first (koff carries -kKfHi x PB);
+// returns kfb's high dword (kKfHi + floor(k_f)).  One v_pk_fma_f32 forms both weights (bitwise
+// the two scalar fmas: f * (-sL) == (-f) * sL); wc goes to VGPRs by one v_mov_b64 (the compiler
+// emits two v_mov_b32; VOP3P reads one SGPR pair).  max(0, w) is the fma's clamp to [0, 1]: the
+// host scales ws, wc by 2^-wexp so that w <= L 2^-wexp <= 1 (wexp = 0 for N >= 3), undone
+// exactly after the angle loop.
+template <int PB>
+__device__ __forceinline__ unsigned tap_f32(double kfb, const BackAngleC& g, int koff, float& w0, float& w1,
+                                            int& off) {
+  unsigned hi;
+  float2v wc, fv, w;
+  float fu;
+  kf_split(kfb, hi, fu);  // (fu: frac x 2^32; ws carries 2^-32)
+  fv.x = fu;              // op_sel_hi:[0,...] reads the low half for both lanes of the pair
+  asm("v_mov_b64 %0, %1" : "=v"(wc) : "s"(g.wc));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp" : "=v"(w) : "v"(fv), "s"(g.ws), "v"(wc));
+  w0 = w.x;
+  w1 = w.y;
+  off = kf_addr<PB>(hi, koff);
+  return hi;
+}
+// One float64 tap from the position kf > 0 (so floor is the truncating convert): the weights from
+// the angle's full record; returns floor(kf)
+template <typename T>
+__device__ __forceinline__ int tap_f64(double kf, const BackAngle& gd, T& w0, T& w1) {
+  const int k0 = (int)kf;
+  const T f = (T)__builtin_amdgcn_fract(kf);
+  w0 = fmax(T(0), T(1) - f * (T)gd.slope) * (T)gd.L;
+  w1 = fmax(T(0), T(1) - (T(1) - f) * (T)gd.slope) * (T)gd.L;
+  return k0;
+}
+// An angle record through the constant address space: a scalar load even where the LDS-DMA
+// intrinsic hides from the compiler that nothing writes the records (as generic loads they became
+// vector loads whose vmcnt waits also drained the next chunk's DMA).  Field by field: no copy
+// constructor binds an address_space(4) object.
+using BackAngleCRec = const __attribute__((address_space(4))) BackAngleC;
+__device__ __forceinline__ BackAngleC angle_rec(BackAngleCRec* r) {
+  BackAngleC g;
+  g.Bi = r->Bi;
+  g.Bj = r->Bj;
+  g.ws = r->ws;
+  g.wc = r->wc;
+  return g;
+}
 
 // ---------------------------------------------------------------------------
 // vector I/O of VB samples (VB*sizeof(T) contiguous bytes)
@@ -386,13 +431,10 @@ __device__ __forceinline__ void block_reduce_rs_tail(double (&v)[NA], double (&t
 // The block's NT = NQ x (lane-block nodes) dot partials per thread (pq flattened node-major)
 // reduced to out_lds[0 .. NT): unpadded NA + NB when NT is 16k + 1, 2, 4 or 8 (k >= 1),
 // otherwise padded to a multiple of 16 -- the same totals either way
-#ifndef ADMM_RS_TAIL
-#define ADMM_RS_TAIL 1  // 0: always the padded form (A/B builds)
-#endif
 template <int NT>
 struct RsShape {
   static constexpr int NA = (NT / 16) * 16, NB = NT - NA;
-  static constexpr bool SPLIT = ADMM_RS_TAIL && NA >= 16 && (NB == 1 || NB == 2 || NB == 4 || NB == 8);
+  static constexpr bool SPLIT = NA >= 16 && (NB == 1 || NB == 2 || NB == 4 || NB == 8);
   static constexpr int NS = SPLIT ? NT : ((NT + 15) / 16) * 16;  // LDS stride / out_lds size
 };
 template <int NT, int NW>
@@ -1641,12 +1683,6 @@ constexpr int kBAngC = ADMM_BK_ANGC;  // angles per staged sinogram-window chunk
 #ifndef ADMM_DIAG_G
 #define ADMM_DIAG_G 2
 #endif
-#ifndef ADMM_BK_DMA
-#define ADMM_BK_DMA 1  // mirror back projector (H mode): window bins staged by LDS-DMA
-#endif
-#ifndef ADMM_BK_LB2
-#define ADMM_BK_LB2 1  // ... and two lane blocks per block where the grid still fills the chip
-#endif
 constexpr int kDiagG = ADMM_DIAG_G;  // nodes per staging pass of the DIAG epilogue
 constexpr int kDiagScratch = kDiagG * ((kBTI + 2) * (kBTJ + 2) + 2 * (kBTI + 1) * (kBTJ + 1));
 template <typename T, int VB, int VS = VB>
@@ -1804,28 +1840,9 @@ void k_back(BackArgs<T> A) {
                  int tt) {
     int k0, off;
     if constexpr (std::is_same<T, float>::value) {
-      // one v_pk_fma_f32 for both taps (bitwise the two scalar fmas: f * (-sL) == (-f) * sL)
-      // wc to VGPRs by one v_mov_b64 (the compiler emits two v_mov_b32; VOP3P reads one SGPR
-      // pair).  max(0, w) is the fma's clamp to [0, 1]: the host scales ws, wc by 2^-wexp so
-      // that w <= L 2^-wexp <= 1 (wexp = 0 for N >= 3), undone exactly after the angle loop
-      unsigned hi;
-      float2v wc, fv, w;
-      float fu;
-      kf_split(fma(xi, g.Bi, fma(yj, g.Bj, Kcb)), hi, fu);  // (fu: frac x 2^32; ws carries 2^-32)
-      fv.x = fu;  // op_sel_hi:[0,...] reads the low half for both lanes of the pair
-      asm("v_mov_b64 %0, %1" : "=v"(wc) : "s"(g.wc));
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp" : "=v"(w) : "v"(fv), "s"(g.ws), "v"(wc));
-      w0 = w.x;
-      w1 = w.y;
-      k0 = (int)(hi - kKfHi);
-      off = kf_addr<PB>(hi, koff);  // (koff carries -kKfHi x PB)
+      k0 = (int)(tap_f32<PB>(fma(xi, g.Bi, fma(yj, g.Bj, Kcb)), g, koff, w0, w1, off) - kKfHi);
     } else {
-      const double kf = fma(xi, g.Bi, fma(yj, g.Bj, Kc));
-      k0 = (int)kf;  // == floor(kf): kf > 0
-      const T f = (T)__builtin_amdgcn_fract(kf);
-      const BackAngle& gd = A.ang[t0c + tt];
-      w0 = fmax(T(0), T(1) - f * (T)gd.slope) * (T)gd.L;
-      w1 = fmax(T(0), T(1) - (T(1) - f) * (T)gd.slope) * (T)gd.L;
+      k0 = tap_f64(fma(xi, g.Bi, fma(yj, g.Bj, Kc)), A.ang[t0c + tt], w0, w1);
       off = k0 * PB + koff;
     }
     if constexpr (MODE == BACK_WSQ) {
@@ -2049,13 +2066,20 @@ void k_back(BackArgs<T> A) {
 // the real lane block of both pixels (back_epilogue / diag_epilogue_tile with VS = VBR lanes per
 // real vector).  Two LDS windows per angle (upper tile, mirror tile) at half the angles per
 // chunk keep the LDS size and the staged bytes per tap of k_back.
+//
+// LB lane blocks per block (back_mirror_body's LB; 2 in k_back_mirror_2, H mode, float32,
+// LDS-DMA): the same pixel tile of lane blocks LB z .. LB z + LB - 1.  A tap's position, weights
+// and LDS address are formed once and applied to every lane block's windows (at LB = 2 the
+// per-tap overhead is paid per 8 real nodes instead of 4), at 1/LB of the angles per chunk (the
+// LB lane blocks' windows fill the same 98 KB) and 1/LB as many blocks.  Per lane block the
+// arithmetic and its order do not depend on LB: bitwise the same Hp and dot partials.
 // ===========================================================================
 // the mirror back projector of (T, VB, MODE) stages its windows by LDS-DMA (H mode, 16-byte
 // window packs) unless instantiated with DMAQ = false (the register-staged windows: A/B and the
 // bitwise test, ADMM_BK_STAGING=reg at context creation)
 template <typename T, int VB, int MODE>
 constexpr bool back_mirror_dma() {
-  return ADMM_BK_DMA && MODE == BACK_H && Planes<T, VB>::NPL == 2 && sizeof(Pack<T, Planes<T, VB>::PV>) == 16;
+  return MODE == BACK_H && Planes<T, VB>::NPL == 2 && sizeof(Pack<T, Planes<T, VB>::PV>) == 16;
 }
 // The H epilogue's p stencil from LDS (float32, LDS-DMA kernels; ADMM_BK_EPI=global at context
 // creation keeps the global loads: A/B and the bitwise test).  Per-pixel global loads fetch every
@@ -2101,9 +2125,10 @@ __device__ __forceinline__ void ptile_stage(const BackArgs<T>& A, lds_char* lds,
   }
 }
 
-template <typename T, int VB, int VBR, int MODE, bool DMAQ, bool EPIQ = true>
+template <typename T, int VB, int VBR, int MODE, bool DMAQ, bool EPIQ = true, int LB = 1>
 __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   static_assert(MODE == BACK_H || MODE == BACK_INIT || MODE == BACK_DIAG || MODE == BACK_ATB, "batch modes");
+  static_assert(LB == 1 || LB == 2, "one or two lane blocks per block");
   constexpr int MH = VB / 2, MS = VBR / MH;
   static_assert(VB % 2 == 0 && VBR % MH == 0, "mirror: VB = 2 x (a divisor of VBR)");
   constexpr int NQ = (MODE == BACK_H || MODE == BACK_DIAG) ? 5 : 1;
@@ -2119,9 +2144,7 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   const int i2 = N - 1 - i;                  // the mirror pixel's row
   const bool inb = (i < Nh) && (j < N);
   const bool inb2 = inb && (i2 != i);        // (odd N: the middle row pairs with itself)
-  const int chunk = blockIdx.z, rc = chunk / MS, mq = chunk % MS;
-  const int v0 = rc * VBR + mq * MH;         // first real node of this lane block
-  const int nv = min(MH, A.V - v0);
+  const int z0 = (int)blockIdx.z * LB;       // the block's first lane block
   const double c0 = 0.5 * (N - 1);
   // clamped coordinates keep out-of-tile threads inside the windows; the mirror pixel's
   // x-coordinate is exactly -xi ((N-1-i) - c0 = c0 - i)
@@ -2131,7 +2154,8 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   const double Kc = A.K + (double)kbias;
   const double Kcb = Kc + kKfBias;  // (float taps, kf_split)
   constexpr bool FB = std::is_same<T, float>::value;  // biased window offsets (kf_split)
-  constexpr int ANGC_ = ((NPL > 2) ? kBAngC / 2 : kBAngC) / 2;
+  // angles per chunk: the 2 LB windows of an angle (upper / mirror tile per lane block) in k_back's LDS
+  constexpr int ANGC_ = ((NPL > 2) ? kBAngC / 2 : kBAngC) / (2 * LB);
   constexpr int ANGC_DIAG = (98304 / (2 * NPL * kBWin * PB)) & ~3;
   constexpr int ANGC = (MODE == BACK_DIAG && ANGC_ > ANGC_DIAG) ? ANGC_DIAG : ANGC_;
   static_assert(ANGC % 4 == 0 && ANGC >= 4, "angle chunks are read as int4 groups");
@@ -2143,18 +2167,22 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
   // it; the window offsets (kmin_s) and first bins (kst_s) rotate over three slots, written two
   // chunks ahead.
   constexpr bool DMA = DMAQ && back_mirror_dma<T, VB, MODE>();
-  constexpr int NWB = DMA ? 4 : 2, NKS = DMA ? 3 : 2;
-  constexpr int BUFB = 2 * NPL * ANGC * kBWin * PB;  // bytes of one chunk's windows
-  // the H epilogue's p stencil from a tile staged in win after the taps (ptile_stage)
+  static_assert(LB == 1 || (DMA && std::is_same<T, float>::value), "two lane blocks: float32, H mode, LDS-DMA");
+  constexpr int NWB = (DMA ? 2 : 1) * LB * 2, NKS = DMA ? 3 : 2;
+  constexpr int BUFB = LB * 2 * NPL * ANGC * kBWin * PB;  // bytes of one chunk's windows
+  // the H epilogue's p stencil from tiles staged in win after the taps (ptile_stage)
   constexpr bool EPI = EPIQ && DMA && std::is_same<T, float>::value && MH * sizeof(T) == 16;
-  static_assert(!EPI || ptile_bytes<1>() <= 2 * BUFB, "the p tiles fit in the window array");
-  __shared__ Pack<T, PV> win[NWB][NPL][ANGC][kBWin];  // [buffer x 2 + window (upper / mirror tile)]
+  static_assert(!EPI || ptile_bytes<LB>() <= 2 * BUFB, "the p tiles fit in the window array");
+  __shared__ Pack<T, PV> win[NWB][NPL][ANGC][kBWin];  // [(buffer x LB + lane block) x 2 + window (upper / mirror tile)]
   __shared__ int4 kmin_s[NKS][2][ANGC / 4 + 1];       // [slot][window]: byte offsets koff
   __shared__ int kst_s[DMA ? 3 : 1][2][DMA ? ANGC + 1 : 1];  // DMA: [slot][window] first bin - kbias
-  T acc1[VB], acc2[VB];
+  T acc1[LB][VB], acc2[LB][VB];
 #pragma unroll
-  for (int u = 0; u < VB; ++u) acc1[u] = acc2[u] = T(0);
-  const T* sino_c = A.sino + (size_t)rc * m_full * VBR + mq * MH;  // the real lane block
+  for (int l = 0; l < LB; ++l)
+#pragma unroll
+    for (int u = 0; u < VB; ++u) acc1[l][u] = acc2[l][u] = T(0);
+  // lane block l's part of the sinogram (its real lanes of its real chunk)
+  auto sino_lb = [&](int l) { return A.sino + (size_t)((z0 + l) / MS) * m_full * VBR + ((z0 + l) % MS) * MH; };
   int t0c = 0;
 
   // window offsets of a chunk: per angle and window the floor of the smallest corner k_f
@@ -2180,99 +2208,40 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
     }
     reinterpret_cast<int*>(kmin_s[buf][min(w, 1)])[w < 2 ? a : ANGC] = koff;  // (spare slot)
   };
-  auto kmin_chunk = [&](int t0, int buf) { kmin_store(buf, kmin_load(t0)); };
-  auto kmin_chunk_b = [&](int t0, int buf, int bo) { kmin_store(buf, kmin_load(t0), bo); };
-  constexpr int NE = 2 * ANGC * kBWin * NPL;  // staged packs per chunk
-  constexpr int SPER = (NE + kBkThreads - 1) / kBkThreads;
-  Pack<T, PV> wst[SPER];
-  // (16-byte planes: the window bins as buffer loads at 32-bit offsets from one scalar base; a
-  // bin outside the detector is an out-of-range offset, zero-filled by the hardware)
-  constexpr bool WBUF = NPL == 2 && sizeof(Pack<T, PV>) == 16;
-  const __amdgpu_buffer_rsrc_t rs_sino = [&] {
-    const uint64_t b = (uint64_t)(uintptr_t)sino_c;
+  auto kmin_chunk = [&](int t0, int buf, int bo = 0) { kmin_store(buf, kmin_load(t0), bo); };
+  constexpr int NE = LB * 2 * ANGC * kBWin * NPL;  // staged packs per chunk
+  // a lane block's part of the sinogram as a buffer resource (scalar base)
+  auto sino_rsrc = [&](const T* base) {
+    const uint64_t b = (uint64_t)(uintptr_t)base;
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
     return make_rsrc((const void*)(uintptr_t)(((uint64_t)hi << 32) | lo), (uint32_t)(m_full * VBR * sizeof(T)));
-  }();
-  auto wfetch = [&](int t0, int buf) {
-    const int nt = min(ANGC, n_ang - t0);
-#pragma unroll
-    for (int e = 0; e < SPER; ++e) {
-      const int q = threadIdx.x + e * kBkThreads;
-      const int pl = q % NPL, rest = q / NPL, bin = rest % kBWin, aw = rest / kBWin;
-      const int a = aw % ANGC, w = aw / ANGC;
-      const bool live = q < NE && a < nt;
-      int ko = live ? reinterpret_cast<const int*>(kmin_s[buf][w])[a] : 0;
-      if constexpr (FB) ko = (int)((unsigned)ko + kKfHi * (unsigned)PB);  // the unbiased offset
-      const int k = live ? a * kBWin - ko / PB + bin - kbias : -1;
-      const int t = t0 + a;
-      if constexpr (WBUF) {
-        const int ray = (pl ? 2 * n_ang - 1 - t : t) * n_det + k;
-        const int voff = (live && k >= 0 && k < n_det) ? ray * (VBR * (int)sizeof(T)) : -1;
-        vload<T, PV>(rs_sino, voff, 0, wst[e].v);
-        continue;
-      }
-      const size_t ray0 = (size_t)t * n_det + k, ray1 = (size_t)(2 * n_ang - 1 - t) * n_det + k;
-      if (live && k >= 0 && k < n_det) {
-        if constexpr (NPL == 2) {  // virtual plane pl = orientation pl: one 16-B real plane
-          wst[e] = *reinterpret_cast<const Pack<T, PV>*>(sino_c + (pl ? ray1 : ray0) * VBR);
-        } else {                   // one virtual plane holds both orientations: element gather
-#pragma unroll
-          for (int z = 0; z < PV; ++z) wst[e].v[z] = z < MH ? sino_c[ray0 * VBR + z] : sino_c[ray1 * VBR + z - MH];
-        }
-      } else {
-#pragma unroll
-        for (int z = 0; z < PV; ++z) wst[e].v[z] = T(0);
-      }
-    }
   };
-  auto wcommit = [&](int t0) {
-    const int nt = min(ANGC, n_ang - t0);
-#pragma unroll
-    for (int e = 0; e < SPER; ++e) {
-      const int q = threadIdx.x + e * kBkThreads;
-      const int pl = q % NPL, rest = q / NPL, bin = rest % kBWin, aw = rest / kBWin;
-      const int a = aw % ANGC, w = aw / ANGC;
-      if (q < NE && a < nt) win[w][pl][a][bin] = wst[e];
-    }
-  };
-  // one angle's taps of one pixel from window W (k_back's tap; float: kf is biased, kf_split)
-  auto tap1 = [&](auto wc_, const BackAngleC& g, double kf, int koff, int tt, T(&acc)[VB]) {
+  // one angle's taps of one pixel from window W of every lane block: the weights and the LDS
+  // address once (k_back's tap; float: kf is biased, kf_split), the lane blocks' samples at the
+  // same offset
+  auto tap1 = [&](auto wc_, const BackAngleC& g, double kf, int koff, int tt, T(&acc)[LB][VB]) {
     constexpr int w = decltype(wc_)::value;
-    {
-      T w0, w1;
-      int off;
-      if constexpr (std::is_same<T, float>::value) {
-        unsigned hi;
-        float2v wc, fv, ww;
-        float fu;
-        kf_split(kf, hi, fu);
-        fv.x = fu;
-        asm("v_mov_b64 %0, %1" : "=v"(wc) : "s"(g.wc));
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp" : "=v"(ww) : "v"(fv), "s"(g.ws), "v"(wc));
-        w0 = ww.x;
-        w1 = ww.y;
-        off = kf_addr<PB>(hi, koff);  // (koff carries -kKfHi x PB)
-      } else {
-        const int k0 = (int)kf;  // == floor(kf): kf > 0
-        const T f = (T)__builtin_amdgcn_fract(kf);
-        const BackAngle& gd = A.ang[t0c + tt];
-        w0 = fmax(T(0), T(1) - f * (T)gd.slope) * (T)gd.L;
-        w1 = fmax(T(0), T(1) - (T(1) - f) * (T)gd.slope) * (T)gd.L;
-        off = k0 * PB + koff;
-      }
+    T w0, w1;
+    int off;
+    if constexpr (std::is_same<T, float>::value) {
+      tap_f32<PB>(kf, g, koff, w0, w1, off);  // (koff carries -kKfHi x PB and the DMA buffer's offset)
+    } else {
+      off = tap_f64(kf, A.ang[t0c + tt], w0, w1) * PB + koff;
+    }
+#pragma unroll
+    for (int l = 0; l < LB; ++l)
 #pragma unroll
       for (int q = 0; q < NPL; ++q) {
-        const char* wb = reinterpret_cast<const char*>(&win[w][q][0][0]) + off;
+        const char* wb = reinterpret_cast<const char*>(&win[l * 2 + w][q][0][0]) + off;
         const Pack<T, PV> s0 = *reinterpret_cast<const Pack<T, PV>*>(wb);
         const Pack<T, PV> s1 = *reinterpret_cast<const Pack<T, PV>*>(wb + PB);
 #pragma unroll
         for (int e = 0; e < PV; ++e) {
-          acc[q * PV + e] = fma(w0, s0.v[e], acc[q * PV + e]);
-          acc[q * PV + e] = fma(w1, s1.v[e], acc[q * PV + e]);
+          acc[l][q * PV + e] = fma(w0, s0.v[e], acc[l][q * PV + e]);
+          acc[l][q * PV + e] = fma(w1, s1.v[e], acc[l][q * PV + e]);
         }
       }
-    }
   };
   // both pixels: kf at xi and at -xi (the mirror pixel), sharing the j term
   auto tap2 = [&](const BackAngleC& g, int koff1, int koff2, int tt) {
@@ -2280,76 +2249,56 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
     tap1(std::integral_constant<int, 0>{}, g, fma(xi, g.Bi, inner), koff1, tt, acc1);
     tap1(std::integral_constant<int, 1>{}, g, fma(-xi, g.Bi, inner), koff2, tt, acc2);
   };
-  // one chunk's taps, window offsets from kmin_s[kb]
+  // one chunk's taps, window offsets from kmin_s[kb]; the records at non-negative immediate
+  // offsets of one base (angle_rec: scalar loads)
   auto chunk_taps = [&](int t0, int nt, int kb) {
     t0c = t0;
     int tt = 0;
-    // (records at non-negative immediate offsets of one base, read through the constant address
-    // space: scalar loads even where the LDS-DMA intrinsic hides from the compiler that nothing
-    // writes them -- as generic loads they became vector loads whose vmcnt waits also drained
-    // the next chunk's DMA)
-    using CRec = const __attribute__((address_space(4))) BackAngleC;
-    auto rec = [](CRec* r) {  // field by field (no copy constructor binds an address_space(4) object)
-      BackAngleC g;
-      g.Bi = r->Bi;
-      g.Bj = r->Bj;
-      g.ws = r->ws;
-      g.wc = r->wc;
-      return g;
-    };
-    CRec* gq = (CRec*)(uintptr_t)(A.angc + t0);
+    BackAngleCRec* gq = (BackAngleCRec*)(uintptr_t)(A.angc + t0);
     for (; tt + 4 <= nt; tt += 4, gq += 4) {
       BackAngleC g[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) g[u] = rec(gq + u);
+      for (int u = 0; u < 4; ++u) g[u] = angle_rec(gq + u);
       const int4 k1 = kmin_s[kb][0][tt >> 2], k2 = kmin_s[kb][1][tt >> 2];
       tap2(g[0], k1.x, k2.x, tt);
       tap2(g[1], k1.y, k2.y, tt + 1);
       tap2(g[2], k1.z, k2.z, tt + 2);
       tap2(g[3], k1.w, k2.w, tt + 3);
     }
-    for (; tt < nt; ++tt) {
-      const BackAngleC g = rec((CRec*)(uintptr_t)A.angc + t0 + tt);
-      tap2(g, reinterpret_cast<const int*>(kmin_s[kb][0])[tt], reinterpret_cast<const int*>(kmin_s[kb][1])[tt], tt);
-    }
+    for (; tt < nt; ++tt)
+      tap2(angle_rec(gq + (tt & 3)), reinterpret_cast<const int*>(kmin_s[kb][0])[tt],
+           reinterpret_cast<const int*>(kmin_s[kb][1])[tt], tt);
   };
   if constexpr (DMA) {
-    // this wave's NI 64-slot pieces of a chunk (slot = ((window x NPL + plane) x ANGC + angle)
-    // x kBWin + bin, the windows' LDS order): fixed for the kernel, so their bin / angle /
-    // plane / window are formed once
+    // a chunk's NE slots in the windows' LDS order, slot q = (((lane block x 2 + window) x NPL +
+    // plane) x ANGC + angle) x kBWin + bin, go in 64-slot pieces, NI per wave; a piece lies in one
+    // (lane block, window, plane), so those are wave-uniform and the lane block's own part of
+    // the sinogram is the piece's buffer resource
     constexpr int NI = NE / (64 * kBkWaves);
-    static_assert(NE % (64 * kBkWaves) == 0, "whole 64-slot pieces per wave");
-    const int wvu = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    int pbin[NI], pang[NI], pwin[NI];
-    bool pmir[NI];
-#pragma unroll
-    for (int e = 0; e < NI; ++e) {
-      const int q = (wvu * NI + e) * 64 + lane;
-      pbin[e] = q % kBWin;
-      const int rest = q / kBWin;
-      pang[e] = rest % ANGC;
-      pmir[e] = (rest / ANGC) % NPL;
-      pwin[e] = rest / (ANGC * NPL);
-    }
+    static_assert(NE % (64 * kBkWaves) == 0 && (ANGC * kBWin) % 64 == 0, "whole pieces, one (lane block, window, plane) each");
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
     auto dma = [&](int t0, int ks, int bo) {
       const int nt = min(ANGC, n_ang - t0);
 #pragma unroll
       for (int e = 0; e < NI; ++e) {
-        const int a = pang[e], t = t0 + a;
-        const int k = kst_s[ks][pwin[e]][a] + pbin[e];
-        const int ray = (pmir[e] ? 2 * n_ang - 1 - t : t) * n_det + k;
+        const int q0 = (wvu * NI + e) * 64;
+        const int q = q0 + lane;
+        const int bin = q % kBWin, a = (q / kBWin) % ANGC;
+        const int lwp = q0 / (ANGC * kBWin), pl = lwp % NPL, w = (lwp / NPL) % 2, l = lwp / (2 * NPL);
+        const __amdgpu_buffer_rsrc_t rs = sino_rsrc(sino_lb(l));
+        const int t = t0 + a;
+        const int k = kst_s[ks][w][a] + bin;
+        const int ray = (pl ? 2 * n_ang - 1 - t : t) * n_det + k;
         // bins off the detector (and angles past a short last chunk) are out-of-range offsets:
         // the hardware writes zeros
         const unsigned voff = (a < nt && k >= 0 && k < n_det) ? (unsigned)ray * (unsigned)(VBR * sizeof(T)) : 0xFFFFFFFFu;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rs_sino,
-            (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(&win[0][0][0][0]) + bo +
-                                                       (wvu * NI + e) * 64 * PB),
-            16, voff, 0, 0, 0);
+            rs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(&win[0][0][0][0]) + bo + q0 * PB), 16,
+            voff, 0, 0, 0);
       }
     };
-    kmin_chunk_b(0, 0, 0);
-    if (ANGC < n_ang) kmin_chunk_b(ANGC, 1, BUFB);
+    kmin_chunk(0, 0, 0);
+    if (ANGC < n_ang) kmin_chunk(ANGC, 1, BUFB);
     __syncthreads();
     dma(0, 0, 0);
     __syncthreads();  // (its fence waits for this wave's LDS-DMA) chunk 0 staged
@@ -2369,7 +2318,56 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
       }
     }
   } else {
-    // register-prefetched chunk pipeline (k_back's PF path)
+    // register-prefetched chunk pipeline (k_back's PF path; LB = 1)
+    constexpr int SPER = (NE + kBkThreads - 1) / kBkThreads;
+    Pack<T, PV> wst[SPER];
+    // (16-byte planes: the window bins as buffer loads at 32-bit offsets from one scalar base; a
+    // bin outside the detector is an out-of-range offset, zero-filled by the hardware)
+    constexpr bool WBUF = NPL == 2 && sizeof(Pack<T, PV>) == 16;
+    const T* sino_c = sino_lb(0);
+    const __amdgpu_buffer_rsrc_t rs_sino = sino_rsrc(sino_c);
+    auto wfetch = [&](int t0, int buf) {
+      const int nt = min(ANGC, n_ang - t0);
+  #pragma unroll
+      for (int e = 0; e < SPER; ++e) {
+        const int q = threadIdx.x + e * kBkThreads;
+        const int pl = q % NPL, rest = q / NPL, bin = rest % kBWin, aw = rest / kBWin;
+        const int a = aw % ANGC, w = aw / ANGC;
+        const bool live = q < NE && a < nt;
+        int ko = live ? reinterpret_cast<const int*>(kmin_s[buf][w])[a] : 0;
+        if constexpr (FB) ko = (int)((unsigned)ko + kKfHi * (unsigned)PB);  // the unbiased offset
+        const int k = live ? a * kBWin - ko / PB + bin - kbias : -1;
+        const int t = t0 + a;
+        if constexpr (WBUF) {
+          const int ray = (pl ? 2 * n_ang - 1 - t : t) * n_det + k;
+          const int voff = (live && k >= 0 && k < n_det) ? ray * (VBR * (int)sizeof(T)) : -1;
+          vload<T, PV>(rs_sino, voff, 0, wst[e].v);
+          continue;
+        }
+        const size_t ray0 = (size_t)t * n_det + k, ray1 = (size_t)(2 * n_ang - 1 - t) * n_det + k;
+        if (live && k >= 0 && k < n_det) {
+          if constexpr (NPL == 2) {  // virtual plane pl = orientation pl: one 16-B real plane
+            wst[e] = *reinterpret_cast<const Pack<T, PV>*>(sino_c + (pl ? ray1 : ray0) * VBR);
+          } else {                   // one virtual plane holds both orientations: element gather
+  #pragma unroll
+            for (int z = 0; z < PV; ++z) wst[e].v[z] = z < MH ? sino_c[ray0 * VBR + z] : sino_c[ray1 * VBR + z - MH];
+          }
+        } else {
+  #pragma unroll
+          for (int z = 0; z < PV; ++z) wst[e].v[z] = T(0);
+        }
+      }
+    };
+    auto wcommit = [&](int t0) {
+      const int nt = min(ANGC, n_ang - t0);
+  #pragma unroll
+      for (int e = 0; e < SPER; ++e) {
+        const int q = threadIdx.x + e * kBkThreads;
+        const int pl = q % NPL, rest = q / NPL, bin = rest % kBWin, aw = rest / kBWin;
+        const int a = aw % ANGC, w = aw / ANGC;
+        if (q < NE && a < nt) win[w][pl][a][bin] = wst[e];
+      }
+    };
     kmin_chunk(0, 0);
     __syncthreads();
     wfetch(0, 0);
@@ -2390,273 +2388,32 @@ __device__ __forceinline__ void back_mirror_body(const BackArgs<T>& A) {
       }
     }
   }
-  if constexpr (std::is_same<T, float>::value) {
-    if (A.wexp != 0) {
-#pragma unroll
-      for (int u = 0; u < VB; ++u) {
-        acc1[u] = ldexpf(acc1[u], A.wexp);
-        acc2[u] = ldexpf(acc2[u], A.wexp);
-      }
-    }
-  }
-  // the real A^T s of both pixels: angles < a/2 from the pixel itself, angles >= a/2 from the
-  // mirror pixel's mirrored lanes (fixed order: first half + second half)
-  T r1[MH], r2[MH];
-#pragma unroll
-  for (int h = 0; h < MH; ++h) {
-    r1[h] = acc1[h] + acc2[MH + h];
-    r2[h] = acc2[h] + acc1[MH + h];
-  }
-  double pq[MH][NQ];
-#pragma unroll
-  for (int u = 0; u < MH; ++u)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) pq[u][q] = 0.0;
-  if constexpr (MODE == BACK_DIAG) {
-    __shared__ double diag_s[kDiagScratch];
-    diag_epilogue_tile<T, MH, VBR>(A, diag_s, ib, jb, i, j, inb, rc, v0, nv, r1, pq, mq * MH);
-    diag_epilogue_tile<T, MH, VBR>(A, diag_s, N - ib - kBTI, jb, i2, j, inb2, rc, v0, nv, r2, pq, mq * MH);
-  } else if constexpr (EPI) {
-    lds_char* const tb = (lds_char*)&win[0][0][0][0];
-    __syncthreads();  // no wave still reads the last chunk's windows
-    ptile_stage<T, VBR, MH, 1>(A, tb, ib, jb, chunk);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces landed ...
-    __syncthreads();                                  // ... and every other wave's
-    using PT = PTile<T, MH, kPtC>;
-    if (inb) back_epilogue<T, MH, MODE, NQ, VBR, false, PT>(A, i, j, rc, v0, nv, r1, pq, mq * MH, PT{tb, ib - 1, jb - 1});
-    if (inb2)
-      back_epilogue<T, MH, MODE, NQ, VBR, true, PT>(A, i2, j, rc, v0, nv, r2, pq, mq * MH,
-                                                    PT{tb + kPtSlots * 16, N - 1 - ib - kBTI, jb - 1});
-  } else {
-    if (inb) back_epilogue<T, MH, MODE, NQ, VBR>(A, i, j, rc, v0, nv, r1, pq, mq * MH);
-    if (inb2) back_epilogue<T, MH, MODE, NQ, VBR, true>(A, i2, j, rc, v0, nv, r2, pq, mq * MH);
-  }
-  if constexpr (MODE == BACK_H || MODE == BACK_DIAG) {
-    constexpr int NT = MH * NQ, NS = RsShape<NT>::NS;
-    __shared__ double lds[kBkWaves * NS];
-    __shared__ double tot[NS];
-    double flat[NT];
-#pragma unroll
-    for (int u = 0; u < MH; ++u)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) flat[u * NQ + q] = pq[u][q];
-    block_reduce_flat<NT, kBkWaves>(flat, lds, tot);
-    const int t = threadIdx.x;
-    if (t < MH * NQ && t / NQ < nv) {
-      const int P = gridDim.x * gridDim.y;
-      const int b = blockIdx.y * gridDim.x + blockIdx.x;
-      A.part[((size_t)v0 * NQ + t) * P + b] = tot[t];
-    }
-  }
-}
-
-// the kernels: windows by LDS-DMA where back_mirror_dma (the default), register-staged
-// (k_back_mirror_reg, ADMM_BK_STAGING=reg at context creation; the same results bit for bit)
-template <typename T, int VB, int VBR, int MODE>
-__global__ __launch_bounds__(kBkThreads) void k_back_mirror(BackArgs<T> A) {
-  back_mirror_body<T, VB, VBR, MODE, true>(A);
-}
-template <typename T, int VB, int VBR, int MODE>
-__global__ __launch_bounds__(kBkThreads) void k_back_mirror_reg(BackArgs<T> A) {
-  back_mirror_body<T, VB, VBR, MODE, false>(A);
-}
-// LDS-DMA windows, the H epilogue's p stencil by global loads (ADMM_BK_EPI=global)
-template <typename T, int VB, int VBR, int MODE>
-__global__ __launch_bounds__(kBkThreads) void k_back_mirror_gepi(BackArgs<T> A) {
-  back_mirror_body<T, VB, VBR, MODE, true, false>(A);
-}
-
-// ===========================================================================
-// Mirror back projector, H mode, two lane blocks per block (round 6, `ADMM_BK_LB2`): the same
-// pixel tile of lane blocks 2z and 2z + 1 (8 real nodes).  A tap's position, weights and LDS
-// address are formed once and applied to both lane blocks' windows (the per-tap overhead of
-// k_back_mirror is paid per 8 nodes instead of 4), the windows arrive by LDS-DMA as in
-// k_back_mirror's DMA path (half the angles per chunk: the two lane blocks' windows in two
-// buffers fill the same 98 KB), and the grid is half as many blocks.  Per lane block the
-// arithmetic is k_back_mirror's in the same order: bitwise the same Hp and dot partials.
-// After the taps the four p tiles (two lane blocks x upper / mirrored rows, 74 KB) are staged
-// into the window array and the epilogues read their p stencil there (ptile_stage).
-// ===========================================================================
-template <typename T, int VB, int VBR, bool EPI>  // EPI: the p stencil from LDS (ptile_stage)
-__device__ __forceinline__ void back_mirror_2_body(const BackArgs<T>& A) {
-  constexpr int MODE = BACK_H, NQ = 5, LB = 2;
-  constexpr int MH = VB / 2, MS = VBR / MH;
-  static_assert(VB % 2 == 0 && VBR % MH == 0, "mirror: VB = 2 x (a divisor of VBR)");
-  constexpr int NPL = Planes<T, VB>::NPL, PV = Planes<T, VB>::PV;
-  constexpr int PB = (int)sizeof(Pack<T, PV>);
-  static_assert(std::is_same<T, float>::value && NPL == 2 && PB == 16, "float32 16-byte window packs");
-  const int N = A.N, n_det = A.n_det, n_ang = A.n_ang;  // n_ang: the half geometry's a/2 angles
-  const int Nh = (N + 1) / 2;
-  const size_t m_full = (size_t)2 * n_ang * n_det;
-  const int jb = blockIdx.x * kBTJ, ib = blockIdx.y * kBTI;  // upper tile: rows ib .. (< Nh)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j = jb + 16 * (wv % kBkPatchJ) + (lane & 15);
-  const int i = ib + 4 * (wv / kBkPatchJ) + (lane >> 4);
-  const int i2 = N - 1 - i;                  // the mirror pixel's row
-  const bool inb = (i < Nh) && (j < N);
-  const bool inb2 = inb && (i2 != i);        // (odd N: the middle row pairs with itself)
-  const double c0 = 0.5 * (N - 1);
-  const double xi = (double)min(i, Nh - 1) - c0, yj = (double)min(j, N - 1) - c0;
-  const int jhi = min(jb + kBTJ - 1, N - 1), ihi = min(ib + kBTI - 1, Nh - 1);
-  const int kbias = A.kbias;
-  const double Kc = A.K + (double)kbias;
-  const double Kcb = Kc + kKfBias;  // (kf_split)
-  constexpr int ANGC = kBAngC / 4;  // half of k_back_mirror's: two lane blocks' windows per buffer
-  static_assert(ANGC % 4 == 0 && ANGC >= 4, "angle chunks are read as int4 groups");
-  constexpr int WINB = 2 * NPL * ANGC * kBWin * PB;  // bytes of one lane block's windows per chunk
-  constexpr int BUFB = LB * WINB;                    // bytes of one chunk buffer
-  static_assert(!EPI || (MH * sizeof(T) == 16 && ptile_bytes<LB>() <= 2 * BUFB), "the p tiles fit in the window array");
-  __shared__ Pack<T, PV> win[2 * LB * 2][NPL][ANGC][kBWin];  // [buffer][lane block][window]
-  __shared__ int4 kmin_s[3][2][ANGC / 4 + 1];                // [slot][window]: byte offsets koff
-  __shared__ int kst_s[3][2][ANGC + 1];                      // [slot][window]: first bin - kbias
-  T acc1[LB][VB], acc2[LB][VB];
-#pragma unroll
-  for (int l = 0; l < LB; ++l)
-#pragma unroll
-    for (int u = 0; u < VB; ++u) acc1[l][u] = acc2[l][u] = T(0);
-
-  auto kmin_load = [&](int t0) {
-    const BackAngleC& g = A.angc[min(t0 + ((int)threadIdx.x % ANGC), n_ang - 1)];
-    return make_double2(g.Bi, g.Bj);
-  };
-  auto kmin_store = [&](int ks, double2 bij, int bo) {  // bo: the chunk buffer's byte offset
-    const int w = (int)threadIdx.x / ANGC;  // threads 0 .. 2 ANGC - 1: (window, angle)
-    const double xa = (double)ib - c0, xb = (double)ihi - c0;
-    const double x0 = w ? -xb : xa, x1 = w ? -xa : xb;  // the window's row range (x-coordinates)
-    auto kf = [&](double xx, int jj) { return fma(xx, bij.x, fma((double)jj - c0, bij.y, Kc)); };
-    const double kmn = fmin(fmin(kf(x0, jb), kf(x0, jhi)), fmin(kf(x1, jb), kf(x1, jhi)));
-    const int a = (int)threadIdx.x % ANGC;
-    const int k0w = (int)floor(kmn) - 1;  // the window's first bin (+ kbias)
-    const int koff = (int)((unsigned)((a * kBWin - k0w) * PB) - kKfHi * (unsigned)PB + (unsigned)bo);
-    kst_s[ks][min(w, 1)][w < 2 ? a : ANGC] = k0w - kbias;                      // (spare slot)
-    reinterpret_cast<int*>(kmin_s[ks][min(w, 1)])[w < 2 ? a : ANGC] = koff;
-  };
-  constexpr int NE = LB * 2 * ANGC * kBWin * NPL;  // staged packs per chunk
-  constexpr int NI = NE / (64 * kBkWaves);         // 64-slot pieces per wave
-  static_assert(NE % (64 * kBkWaves) == 0 && (ANGC * kBWin) % 64 == 0, "whole pieces, one (lane block, window, plane) each");
-  const int wvu = __builtin_amdgcn_readfirstlane(wv);
-  auto dma = [&](int t0, int ks, int bo) {
-    const int nt = min(ANGC, n_ang - t0);
-#pragma unroll
-    for (int e = 0; e < NI; ++e) {
-      // slot q = (((lane block x 2 + window) x NPL + plane) x ANGC + angle) x kBWin + bin
-      const int q0 = (wvu * NI + e) * 64;  // a piece lies in one (lane block, window, plane)
-      const int q = q0 + lane;
-      const int bin = q % kBWin, a = (q / kBWin) % ANGC;
-      const int lwp = q0 / (ANGC * kBWin), pl = lwp % NPL, w = (lwp / NPL) % 2, l = lwp / (2 * NPL);
-      const int z = (int)blockIdx.z * LB + l;
-      const T* base = A.sino + (size_t)(z / MS) * m_full * VBR + (z % MS) * MH;  // lane block l
-      const uint64_t b = (uint64_t)(uintptr_t)base;
-      const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-      const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-      const __amdgpu_buffer_rsrc_t rs =
-          make_rsrc((const void*)(uintptr_t)(((uint64_t)hi << 32) | lo), (uint32_t)(m_full * VBR * sizeof(T)));
-      const int t = t0 + a;
-      const int k = kst_s[ks][w][a] + bin;
-      const int ray = (pl ? 2 * n_ang - 1 - t : t) * n_det + k;
-      const unsigned voff = (a < nt && k >= 0 && k < n_det) ? (unsigned)ray * (unsigned)(VBR * sizeof(T)) : 0xFFFFFFFFu;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(&win[0][0][0][0]) + bo + q0 * PB), 16,
-          voff, 0, 0, 0);
-    }
-  };
-  // one angle's taps of one pixel from window W of both lane blocks: the weights and the LDS
-  // address once (k_back_mirror's tap1), the two lane blocks' samples at the same offset
-  auto tap1 = [&](auto wc_, const BackAngleC& g, double kf, int koff, T(&acc)[LB][VB]) {
-    constexpr int w = decltype(wc_)::value;
-    unsigned hi;
-    float2v wc, fv, ww;
-    float fu;
-    kf_split(kf, hi, fu);
-    fv.x = fu;
-    asm("v_mov_b64 %0, %1" : "=v"(wc) : "s"(g.wc));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp" : "=v"(ww) : "v"(fv), "s"(g.ws), "v"(wc));
-    const T w0 = ww.x, w1 = ww.y;
-    const int off = kf_addr<PB>(hi, koff);  // (koff carries -kKfHi x PB and the buffer offset)
-#pragma unroll
-    for (int l = 0; l < LB; ++l)
-#pragma unroll
-      for (int q = 0; q < NPL; ++q) {
-        const char* wb = reinterpret_cast<const char*>(&win[l * 2 + w][q][0][0]) + off;
-        const Pack<T, PV> s0 = *reinterpret_cast<const Pack<T, PV>*>(wb);
-        const Pack<T, PV> s1 = *reinterpret_cast<const Pack<T, PV>*>(wb + PB);
-#pragma unroll
-        for (int e = 0; e < PV; ++e) {
-          acc[l][q * PV + e] = fma(w0, s0.v[e], acc[l][q * PV + e]);
-          acc[l][q * PV + e] = fma(w1, s1.v[e], acc[l][q * PV + e]);
-        }
-      }
-  };
-  auto tap2 = [&](const BackAngleC& g, int koff1, int koff2) {
-    const double inner = fma(yj, g.Bj, Kcb);
-    tap1(std::integral_constant<int, 0>{}, g, fma(xi, g.Bi, inner), koff1, acc1);
-    tap1(std::integral_constant<int, 1>{}, g, fma(-xi, g.Bi, inner), koff2, acc2);
-  };
-  using CRec = const __attribute__((address_space(4))) BackAngleC;
-  auto rec = [](CRec* r) {  // field by field (no copy constructor binds an address_space(4) object)
-    BackAngleC g;
-    g.Bi = r->Bi;
-    g.Bj = r->Bj;
-    g.ws = r->ws;
-    g.wc = r->wc;
-    return g;
-  };
-  auto chunk_taps = [&](int t0, int nt, int ks) {
-    int tt = 0;
-    CRec* gq = (CRec*)(uintptr_t)(A.angc + t0);
-    for (; tt + 4 <= nt; tt += 4, gq += 4) {
-      BackAngleC g[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) g[u] = rec(gq + u);
-      const int4 k1 = kmin_s[ks][0][tt >> 2], k2 = kmin_s[ks][1][tt >> 2];
-      tap2(g[0], k1.x, k2.x);
-      tap2(g[1], k1.y, k2.y);
-      tap2(g[2], k1.z, k2.z);
-      tap2(g[3], k1.w, k2.w);
-    }
-    for (; tt < nt; ++tt)
-      tap2(rec(gq + (tt & 3)), reinterpret_cast<const int*>(kmin_s[ks][0])[tt],
-           reinterpret_cast<const int*>(kmin_s[ks][1])[tt]);
-  };
-  kmin_store(0, kmin_load(0), 0);
-  if (ANGC < n_ang) kmin_store(1, kmin_load(ANGC), BUFB);
-  __syncthreads();
-  dma(0, 0, 0);
-  __syncthreads();  // (its fence waits for this wave's LDS-DMA) chunk 0 staged
-  for (int t0 = 0, ci = 0, ks = 0; t0 < n_ang; t0 += ANGC, ++ci, ks = ks == 2 ? 0 : ks + 1) {
-    const int nt = min(ANGC, n_ang - t0);
-    const double2 rec2 = kmin_load(min(t0 + 2 * ANGC, n_ang - 1));
-    const int ks1 = ks == 2 ? 0 : ks + 1, ks2 = ks1 == 2 ? 0 : ks1 + 1;
-    if (t0 + ANGC < n_ang) dma(t0 + ANGC, ks1, (ci & 1) ? 0 : BUFB);
-    chunk_taps(t0, nt, ks);
-    if (t0 + ANGC < n_ang) {
-      if (t0 + 2 * ANGC < n_ang) kmin_store(ks2, rec2, (ci & 1) ? BUFB : 0);
-      __syncthreads();  // next chunk's DMA landed (fence), this chunk's taps done, slot ks2 visible
-    }
-  }
-  // per lane block: k_back_mirror's epilogue (the real A^T s of both pixels, the fused H epilogue
-  // and the block's 20 dot partials through the same reduction), one lane block at a time
-  constexpr int NT = MH * NQ, NS = RsShape<NT>::NS;
-  __shared__ double lds[kBkWaves * NS];
-  __shared__ double tot[NS];
-  const int P = gridDim.x * gridDim.y;
-  const int b = blockIdx.y * gridDim.x + blockIdx.x;
-  lds_char* const tb = (lds_char*)&win[0][0][0][0];
+  const int P = gridDim.x * gridDim.y;                 // the partials' row length ...
+  const int b = blockIdx.y * gridDim.x + blockIdx.x;  // ... and this block's slot
+  // After the taps the window array holds nothing: the 2 LB p tiles (per lane block the upper
+  // and the mirrored rows) are staged there and the H epilogues read their p stencil from them
+  [[maybe_unused]] lds_char* const tb = (lds_char*)&win[0][0][0][0];
   if constexpr (EPI) {
     __syncthreads();  // no wave still reads the last chunk's windows
-    ptile_stage<T, VBR, MH, LB>(A, tb, ib, jb, (int)blockIdx.z * LB);
+    ptile_stage<T, VBR, MH, LB>(A, tb, ib, jb, z0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces landed ...
     __syncthreads();                                  // ... and every other wave's
   }
+  // one lane block at a time: the real A^T s of both pixels, the fused epilogue of the upper
+  // pixel, then of the mirror pixel, and the block's dot partials through one reduction
 #pragma unroll
   for (int l = 0; l < LB; ++l) {
-    if (A.wexp != 0) {
+    if constexpr (std::is_same<T, float>::value) {
+      if (A.wexp != 0) {  // undo the weight scaling (a power of two: exact)
 #pragma unroll
-      for (int u = 0; u < VB; ++u) {
-        acc1[l][u] = ldexpf(acc1[l][u], A.wexp);
-        acc2[l][u] = ldexpf(acc2[l][u], A.wexp);
+        for (int u = 0; u < VB; ++u) {
+          acc1[l][u] = ldexpf(acc1[l][u], A.wexp);
+          acc2[l][u] = ldexpf(acc2[l][u], A.wexp);
+        }
       }
     }
+    // angles < a/2 from the pixel itself, angles >= a/2 from the mirror pixel's mirrored lanes
+    // (fixed order: first half + second half)
     T r1[MH], r2[MH];
 #pragma unroll
     for (int h = 0; h < MH; ++h) {
@@ -2668,9 +2425,13 @@ __device__ __forceinline__ void back_mirror_2_body(const BackArgs<T>& A) {
     for (int u = 0; u < MH; ++u)
 #pragma unroll
       for (int q = 0; q < NQ; ++q) pq[u][q] = 0.0;
-    const int z = (int)blockIdx.z * LB + l, rc = z / MS, mq = z % MS;
-    const int v0 = rc * VBR + mq * MH, nv = min(MH, A.V - v0);
-    if constexpr (EPI) {
+    const int z = z0 + l, rc = z / MS, mq = z % MS;
+    const int v0 = rc * VBR + mq * MH, nv = min(MH, A.V - v0);  // the lane block's real nodes
+    if constexpr (MODE == BACK_DIAG) {
+      __shared__ double diag_s[kDiagScratch];
+      diag_epilogue_tile<T, MH, VBR>(A, diag_s, ib, jb, i, j, inb, rc, v0, nv, r1, pq, mq * MH);
+      diag_epilogue_tile<T, MH, VBR>(A, diag_s, N - ib - kBTI, jb, i2, j, inb2, rc, v0, nv, r2, pq, mq * MH);
+    } else if constexpr (EPI) {
       using PT = PTile<T, MH, kPtC>;
       if (inb)
         back_epilogue<T, MH, MODE, NQ, VBR, false, PT>(A, i, j, rc, v0, nv, r1, pq, mq * MH,
@@ -2682,24 +2443,46 @@ __device__ __forceinline__ void back_mirror_2_body(const BackArgs<T>& A) {
       if (inb) back_epilogue<T, MH, MODE, NQ, VBR>(A, i, j, rc, v0, nv, r1, pq, mq * MH);
       if (inb2) back_epilogue<T, MH, MODE, NQ, VBR, true>(A, i2, j, rc, v0, nv, r2, pq, mq * MH);
     }
-    double flat[NT];
+    if constexpr (MODE == BACK_H || MODE == BACK_DIAG) {
+      constexpr int NT = MH * NQ, NS = RsShape<NT>::NS;
+      __shared__ double lds[kBkWaves * NS];
+      __shared__ double tot[NS];
+      double flat[NT];
 #pragma unroll
-    for (int u = 0; u < MH; ++u)
+      for (int u = 0; u < MH; ++u)
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) flat[u * NQ + q] = pq[u][q];
-    block_reduce_flat<NT, kBkWaves>(flat, lds, tot);
-    const int t = threadIdx.x;
-    if (t < NT && t / NQ < nv) A.part[((size_t)v0 * NQ + t) * P + b] = tot[t];
+        for (int q = 0; q < NQ; ++q) flat[u * NQ + q] = pq[u][q];
+      block_reduce_flat<NT, kBkWaves>(flat, lds, tot);
+      const int t = threadIdx.x;
+      if (t < NT && t / NQ < nv) A.part[((size_t)v0 * NQ + t) * P + b] = tot[t];
+    }
   }
+}
+
+// The kernels.  k_back_mirror: one lane block per block, windows by LDS-DMA where back_mirror_dma;
+// k_back_mirror_reg: register-staged windows (ADMM_BK_STAGING=reg at context creation; the same
+// results bit for bit); k_back_mirror_2: two lane blocks per block where the grid still fills
+// the chip (H mode, float32, LDS-DMA; ADMM_BK_STAGING=dma2 forces it, dma1 forbids it);
+// *_gepi: the H epilogue's p stencil by global loads (ADMM_BK_EPI=global).
+template <typename T, int VB, int VBR, int MODE>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror(BackArgs<T> A) {
+  back_mirror_body<T, VB, VBR, MODE, true>(A);
+}
+template <typename T, int VB, int VBR, int MODE>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror_reg(BackArgs<T> A) {
+  back_mirror_body<T, VB, VBR, MODE, false>(A);
+}
+template <typename T, int VB, int VBR, int MODE>
+__global__ __launch_bounds__(kBkThreads) void k_back_mirror_gepi(BackArgs<T> A) {
+  back_mirror_body<T, VB, VBR, MODE, true, false>(A);
 }
 template <typename T, int VB, int VBR>
 __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2(BackArgs<T> A) {
-  back_mirror_2_body<T, VB, VBR, true>(A);
+  back_mirror_body<T, VB, VBR, BACK_H, /*DMAQ*/ true, /*EPIQ*/ true, /*LB*/ 2>(A);
 }
-// the H epilogue's p stencil by global loads (ADMM_BK_EPI=global)
 template <typename T, int VB, int VBR>
 __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2_gepi(BackArgs<T> A) {
-  back_mirror_2_body<T, VB, VBR, false>(A);
+  back_mirror_body<T, VB, VBR, BACK_H, /*DMAQ*/ true, /*EPIQ*/ false, /*LB*/ 2>(A);
 }
 
 // ===========================================================================
@@ -2746,13 +2529,10 @@ __device__ __forceinline__ void tile_store_T(TileT<T, VB>& tl, T* __restrict__ o
 // (BACK_INIT's epilogue with its projected A^T A xs replaced; xs and its four neighbours
 // are (T) x read straight from x), p also written transposed.  One thread per pixel, all
 // VB nodes of the chunk; a block is kTile x kCgRows pixels (the CG update's grid).
-// ADMM_SR_LDS: the block stages (T) x of its tile plus a one-pixel halo per node in LDS once
+// The block stages (T) x of its tile plus a one-pixel halo per node in LDS once
 // (the tile's 32 aligned columns of every row first, then the two halo columns) and the
 // stencil reads it there -- 2 float64 loads per thread and node instead of 5, the same casts
 // in the same order.
-#ifndef ADMM_SR_LDS
-#define ADMM_SR_LDS 1
-#endif
 template <typename T, int VB>
 __global__ __launch_bounds__(kBlock) void k_start_reuse(
     const T* __restrict__ ats, const double* __restrict__ x, EdgeIn E, const double* __restrict__ q,
@@ -2768,7 +2548,6 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
   const int jj = threadIdx.x % kTile, ii = threadIdx.x / kTile;
   const int i0 = blockIdx.y * ROWS, j0 = blockIdx.x * kTile;
   const int i = i0 + ii, j = j0 + jj;
-#if ADMM_SR_LDS
   __shared__ T xt[VB][ROWS + 2][kTile + 2];  // (T) x over rows i0 - 1 .., columns j0 - 1 ..; 0 off the image
   {
     constexpr int NIN = (ROWS + 2) * kTile, NEL = (ROWS + 2) * (kTile + 2);
@@ -2796,7 +2575,6 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
       }
     __syncthreads();
   }
-#endif
   if (i < N && j < N) {
     const int pix = i * N + j;
     T av[VB], outv[VB];
@@ -2814,22 +2592,12 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
         }
         cvec[vo + pix] = cc;
         // K^T K xs at (i, j) from (T) x, in BACK_INIT's order
-#if ADMM_SR_LDS
         const double pcd = (double)xt[u][ii + 1][jj + 1];
         double ktk = 0.0;
         if (i >= 1) ktk += pcd - (double)xt[u][ii][jj + 1];
         if (i <= N - 2) ktk -= (double)xt[u][ii + 2][jj + 1] - pcd;
         if (j >= 1) ktk += pcd - (double)xt[u][ii + 1][jj];
         if (j <= N - 2) ktk -= (double)xt[u][ii + 1][jj + 2] - pcd;
-#else
-        const double* xv = x + vo;
-        const double pcd = (double)(T)xv[pix];
-        double ktk = 0.0;
-        if (i >= 1) ktk += pcd - (double)(T)xv[pix - N];
-        if (i <= N - 2) ktk -= (double)(T)xv[pix + N] - pcd;
-        if (j >= 1) ktk += pcd - (double)(T)xv[pix - 1];
-        if (j <= N - 2) ktk -= (double)(T)xv[pix + 1] - pcd;
-#endif
         const double ab = atb[vo + pix];
         const double h = ((double)av[u] + ab) + rho * dsum[vo + pix] * pcd + mu * ktk;
         const double rr = ab + rho * cc + mu * kt_w_at(dvar + 2 * vo, evar + 2 * vo, N, i, j) - h;
@@ -3012,9 +2780,6 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 // The CG directions whose x steps the fused TV update applies (FUSE): p[k] with alpha_k
 // from the reduction redH + k * 5V, k = 0 .. K-1 (K = 1: only the round's last step).
 constexpr int kMaxCgRing = 8;
-#ifndef ADMM_TV_ALIGN
-#define ADMM_TV_ALIGN 1
-#endif
 template <typename T>
 struct PRing {
   const T* p[kMaxCgRing];
@@ -3094,7 +2859,6 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
     }
     __syncthreads();
     for (int q = threadIdx.x; q < PR * PC; q += kTvThreads) {
-#if ADMM_TV_ALIGN
       // the tile's kTvTile columns first (rows of 256-B-aligned float64 runs per node), the two
       // halo columns after them: no lane group straddles a cache line
       int rr, cc;
@@ -3106,9 +2870,6 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
         rr = h >> 1;
         cc = (h & 1) ? PC - 1 : 0;
       }
-#else
-      const int rr = q / PC, cc = q % PC;
-#endif
       const int i = i0 - 1 + rr, j = j0 - 1 + cc;
       if (i < 0 || j < 0 || i >= N || j >= N) continue;
       const int o = i * N + j;
@@ -3155,7 +2916,6 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
     // column-fastest: a wave reads runs of 33 consecutive pixels of one node
     __shared__ double qx_s[HR][VB][HC], qy_s[HR][VB][HC];
     for (int q = threadIdx.x; q < HR * HC * VB; q += kTvThreads) {
-#if ADMM_TV_ALIGN
       // (as above: the kTvTile tile columns of every (row, node) first, the halo column after)
       int cc, u, rr;
       if (q < HR * VB * kTvTile) {
@@ -3169,10 +2929,6 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
         u = h % VB;
         rr = h / VB;
       }
-#else
-      const int cc = q % HC, rest = q / HC;
-      const int u = rest % VB, rr = rest / VB;  // halo-shifted (row 0 = i0-1, col 0 = j0-1)
-#endif
       const int i = i0 + rr - 1, j = j0 + cc - 1;
       const int vq = chunk * VB + u;
       if (vq >= V || i < 0 || j < 0 || i >= N || j >= N) continue;

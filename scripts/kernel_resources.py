@@ -10,6 +10,8 @@ want = sys.argv[2:]
 for blk in re.split(r"\n  - ", meta)[1:]:
     f = dict(re.findall(r"^\s+\.([a-z_]+):\s+(\S+)", blk, re.M))
     name = f.get("name", "?")
+    if "vgpr_count" not in f:  # (the document's trailing target / version entries: not a kernel)
+        continue
     if want and not any(w in name for w in want):
         continue
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()

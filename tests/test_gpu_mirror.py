@@ -120,7 +120,8 @@ def test_default_mode_by_sample_type(cuda, monkeypatch):
 def test_projector_block_shapes_bitwise(cuda, monkeypatch, dtype, V, N):
     """The mirror back projector's H mode stages its sinogram windows by LDS-DMA into two
     chunk buffers (kernels.hpp k_back_mirror, DMA), and where the grid fills the chip runs two
-    lane blocks per block (k_back_mirror_2); ADMM_BK_STAGING at context creation selects
+    lane blocks per block (k_back_mirror_2: the same back_mirror_body at LB = 2, so this test
+    compares instantiations of one body); ADMM_BK_STAGING at context creation selects
     "dma1" (one lane block per block), "reg" (register-staged windows) or "dma2" (two lane
     blocks wherever they pair up).  The same bins land in LDS and every lane block's taps read
     them in the same order: whole trajectories bitwise equal (5 nodes = a full and a one-node
