@@ -40,8 +40,9 @@ import torch.distributed as dist
 
 from .exchange import split_stats
 from .fbp import FILTERS, fbp
-from .geometry import RayTransform
+from .geometry import CSR_WEIGHTS_MSG, RayTransform
 from .groups import RankGroups
+from .solver import node_ray_weights
 from ._lib import NODE_STATS as _NODE_STATS
 from .matrix import MatrixOperator, as_operators
 from .metrics import check_data_range, check_metrics, check_side, _check_mask_shape
@@ -91,8 +92,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
              pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
-             metrics_mask=None):
-    """``metrics``: None, or a subset of ("psnr", "ssim"): after every iteration's x-update each
+             metrics_mask=None, ray_weights=None):
+    """``ray_weights``: per-ray weights omega of the data term, 1/2 sum_r omega_r (A x - b)_r^2
+    (weighted least squares; omega = 0 masks a ray): None, one (m,) / (angles, det) array for every
+    node, or one entry (array, tensor or None) per graph node; finite and >= 0, checked on the host
+    before any device work; geometry operators only.  ``sino_mse`` then records the weighted sum.
+    With None nothing changes: no call, no buffer, identical histories.
+    ``metrics``: None, or a subset of ("psnr", "ssim"): after every iteration's x-update each
     node's image is scored against ``phantom_true`` (required then) on the GPU (admm_hip.metrics,
     admm_image_metrics on the batch's stream) and the history gains ``psnr_per_node`` / ``psnr_mean``
     and / or ``ssim_per_node`` / ``ssim_mean`` (one V_total array / its mean per iteration); the
@@ -142,6 +148,10 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     if not mu > 0:
         raise ValueError("mu must be > 0 (set lam_tv > 0 or pass mu explicitly)")
     start = _parse_x_init(x_init, A_dense_list, V_total, N)  # argument errors on every rank alike
+    if ray_weights is not None:
+        for g, A in enumerate(A_dense_list):
+            if node_ray_weights(ray_weights, [g], A.geom.m) is not None and hasattr(A.geom, "create_ctx"):
+                raise ValueError(CSR_WEIGHTS_MSG)
     world, rank = _dist_info(group)
     torch.cuda.set_device(A_dense_list[0].device)
     if snapshot_dir is not None:
@@ -151,7 +161,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     rg = RankGroups(A_dense_list, G, V_total, world, rank, sinograms, Qij_diag_fn, rho, lam_tv, mu,
                     tv_iters, cg_iters, tv_kind, phantom_true, fusion=fusion, Wi_list=Wi_list,
                     keep_x=inner_tol is None, group=group, streams=streams,  # this loop never writes x itself
-                    derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state])
+                    derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state],
+                    ray_weights=ray_weights)
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
     if start is not None:

@@ -132,12 +132,22 @@ class QProvider:
         return (self.q_mode, min(a, b), max(a, b))
 
 
-def make_precisions(ops: list[RayTransform], q_mode: str = "arithmetic"):
+def make_precisions(ops: list[RayTransform], q_mode: str = "arithmetic", ray_weights=None):
     """(Wi_list, Qij_diag) with W from the HIP kernel (block_3_graph_and_precisions.py:11-43).
-    ``ops`` may also hold matrices (the reference's dense A_dense_list): matrix.as_operators."""
+    ``ops`` may also hold matrices (the reference's dense A_dense_list): matrix.as_operators.
+    ``ray_weights`` (solver.node_ray_weights: None, one array for every node, or one entry per
+    node): W_i[p] = max(sum_r omega_i,r A_i[r,p]^2, 1e-12), the weighted data term's precisions;
+    nodes with weights get a W (and Q slots) of their own."""
     from .matrix import as_operators
+    from .solver import node_ray_weights
+    ops = as_operators(ops)
     cache, Wi_list, keys = {}, [], []
-    for A in as_operators(ops):
+    for i, A in enumerate(ops):
+        wts = node_ray_weights(ray_weights, [i], A.geom.m)
+        if wts is not None:
+            Wi_list.append(A.column_norms_sq(as_numpy=True, ray_weights=wts[i]))
+            keys.append(len(ops) + i)  # (a key of its own, past every shared one)
+            continue
         key = (A.geom, A.dtype, A.device)
         if key not in cache:
             cache[key] = (len(cache), A.column_norms_sq(as_numpy=True))
@@ -145,3 +155,17 @@ def make_precisions(ops: list[RayTransform], q_mode: str = "arithmetic"):
         Wi_list.append(W)
         keys.append(k)
     return Wi_list, QProvider(Wi_list, q_mode, keys)
+
+
+def transmission_data(sino_clean, I0: float, generator=None):
+    """Transmission measurements of the line integrals ``sino_clean`` at ``I0`` incident photons
+    per ray: counts ~ Poisson(I0 exp(-sino)), the log data b = -log(max(counts, 1) / I0) and its
+    statistical weights omega = counts / I0 (the inverse variance of b up to the factor I0: PWLS;
+    a ray that counted nothing has omega = 0).  Returns (b, omega), tensors of ``sino_clean``'s
+    shape, dtype and device; ``generator``: a torch.Generator on that device (seeded: repeatable)."""
+    s = torch.as_tensor(sino_clean)
+    if not (I0 > 0):
+        raise ValueError("I0 must be > 0")
+    counts = torch.poisson(float(I0) * torch.exp(-s.to(torch.float64)), generator=generator)
+    b = -torch.log(torch.clamp(counts, min=1.0) / float(I0))
+    return b.to(s.dtype), (counts / float(I0)).to(s.dtype)

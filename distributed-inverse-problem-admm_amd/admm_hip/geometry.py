@@ -67,6 +67,25 @@ def _torch():
     return torch
 
 
+CSR_WEIGHTS_MSG = ("per-ray weights are not supported for explicit-matrix operators: scale the rows of A "
+                   "and the sinogram by sqrt(weights) instead (exact there)")
+
+
+def ray_weights_host(w, m: int, what: str = "ray_weights") -> np.ndarray:
+    """Per-ray weights ``w`` ((m,) or (angles, det) array or tensor) as a flat float64 host
+    array, checked once: ``m`` entries, finite and >= 0 (ValueError otherwise)."""
+    torch = _torch()
+    a = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    if a.size != m:
+        raise ValueError(f"{what} has {a.size} entries, expected {m} (one per ray)")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{what} must be finite")
+    if np.any(a < 0):
+        raise ValueError(f"{what} must be >= 0")
+    return a
+
+
 def default_device() -> int:
     """The calling process's current HIP device (torch.cuda.current_device()): with one
     process per GPU and ``torch.cuda.set_device(local_rank)`` first, every operator a rank
@@ -190,10 +209,25 @@ class RayTransform:
             return out.double().cpu().numpy() if np.asarray(x).dtype == np.float64 else out.cpu().numpy()
         return out
 
-    def column_norms_sq(self, as_numpy: bool = True):
-        """W[p] = max(sum_r A[r,p]^2, 1e-12)  (make_precisions, block_3:20-23)."""
+    def column_norms_sq(self, as_numpy: bool = True, ray_weights=None):
+        """W[p] = max(sum_r A[r,p]^2, 1e-12)  (make_precisions, block_3:20-23); with
+        ``ray_weights`` omega ((m,) or (angles, det), finite, >= 0): max(sum_r omega_r A[r,p]^2,
+        1e-12), the precision of the weighted data term (admm_column_norms_sq_weighted)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
+        if ray_weights is not None:
+            if hasattr(self.geom, "create_ctx"):
+                raise ValueError(CSR_WEIGHTS_MSG)
+            wh = ray_weights_host(ray_weights, self.geom.m)
+            w = torch.as_tensor(wh).to(device=dev, dtype=self._tdtype())
+            W = torch.empty(self.geom.n, device=dev, dtype=torch.float64)
+            ctx = self.ctx
+            _lib.check(ctx.lib.admm_column_norms_sq_weighted(ctx.h, C.c_void_p(w.data_ptr()),
+                                                             C.c_void_p(W.data_ptr()),
+                                                             C.c_void_p(current_stream_handle(dev))),
+                       "admm_column_norms_sq_weighted")
+            torch.cuda.current_stream(dev).synchronize()  # (w is released on return)
+            return W.cpu().numpy() if as_numpy else W
         W = torch.empty(self.geom.n, device=dev, dtype=torch.float64)
         ctx = self.ctx
         _lib.check(ctx.lib.admm_column_norms_sq(ctx.h, C.c_void_p(W.data_ptr()),

@@ -135,8 +135,9 @@ def run_hbm_bytes(device, world: int, group=None, collective: bool = True) -> in
 class RankGroups:
     def __init__(self, A_list, G, V_total: int, world: int, rank: int, sinograms, Qij_diag_fn,
                  rho, lam, mu, tv_iters, cg_iters, tv_kind, phantom, fusion="midpoint", Wi_list=None,
-                 keep_x=False, group=None, halo=True, streams=1, derive_z=None):
-        """``halo=False``: no inter-rank exchange (bench.py's per-rank proxy: one rank's share
+                 keep_x=False, group=None, halo=True, streams=1, derive_z=None, ray_weights=None):
+        """``ray_weights``: per-ray weights of the data term by global node (solver.node_ray_weights);
+        every batch takes its own nodes' entries.  ``halo=False``: no inter-rank exchange (bench.py's per-rank proxy: one rank's share
         of a ``world``-rank run on one GPU, its halo rows held fixed).  ``streams`` > 1: every
         operator group of at least 2 x SPLIT_MIN nodes is split into up to that many near-equal
         batches whose x-updates (and edge updates) run concurrently on their own HIP streams,
@@ -191,7 +192,7 @@ class RankGroups:
             geom, dtype, device = k[0]
             self.batches.append(NodeBatch(geom, dtype, gp, sinograms, Qij_diag_fn, rho, lam, mu, tv_iters,
                                           cg_iters, tv_kind, phantom, device, fusion=fusion, Wi_list=Wi_list,
-                                          keep_x=keep_x, derive_z=self.derive_z))
+                                          keep_x=keep_x, derive_z=self.derive_z, ray_weights=ray_weights))
         self.device = self.batches[0].dev
         if len(self.batches) == 1:
             self.x_rank = self.batches[0].x_ext

@@ -149,8 +149,12 @@ class MatrixOperator:
         torch = _torch()
         return torch.float64 if self.dtype == "float64" else torch.float32
 
-    def column_norms_sq(self, as_numpy: bool = True):
-        """W[p] = max(sum_r A[r,p]^2, 1e-12)  (make_precisions, block_3:20-23)."""
+    def column_norms_sq(self, as_numpy: bool = True, ray_weights=None):
+        """W[p] = max(sum_r A[r,p]^2, 1e-12)  (make_precisions, block_3:20-23).  Per-ray weights
+        are for geometry operators only: scale the rows of an explicit matrix instead."""
+        if ray_weights is not None:
+            from .geometry import CSR_WEIGHTS_MSG
+            raise ValueError(CSR_WEIGHTS_MSG)
         torch = _torch()
         dev = torch.device("cuda", self.device)
         W = torch.empty(self.geom.n, device=dev, dtype=torch.float64)

@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import ParallelBeamGeometry, RayTransform, current_stream_handle, _Ctx
+from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
+                       ray_weights_host, _Ctx)
 from .plan import ShardPlan, z_is_stored
 
 
@@ -39,12 +40,33 @@ def _vec_key(t: torch.Tensor):
     return ("hash", h)
 
 
+def node_ray_weights(ray_weights, nodes, m: int):
+    """``ray_weights`` (None, one array broadcast to every node, or a per-global-node sequence
+    whose entries are None or an (m,) / (angles, det) array or tensor) as checked float64 host
+    arrays {g: (m,)} for ``nodes`` (None entries left out), or None when no node of ``nodes`` has
+    weights.  Raises ValueError on a wrong length or a negative / non-finite weight."""
+    if ray_weights is None:
+        return None
+    if isinstance(ray_weights, (list, tuple)):
+        get = lambda g: ray_weights[g] if g < len(ray_weights) else None  # noqa: E731
+        out = {g: ray_weights_host(get(g), m, f"ray_weights[{g}]") for g in nodes if get(g) is not None}
+        return out or None
+    w = ray_weights_host(ray_weights, m)
+    return {g: w for g in nodes}
+
+
 class NodeBatch:
     def __init__(self, geom: ParallelBeamGeometry, dtype: str, plan: ShardPlan, sinograms,
                  Qij_diag_fn, rho: float, lam: float, mu: float, tv_iters: int = 10,
                  cg_iters: int = 5, tv_kind: str = "iso", phantom=None, device: int = 0,
-                 fusion: str = "midpoint", Wi_list=None, keep_x: bool = False, derive_z: bool | None = None):
-        """``derive_z``: z_ij is not stored but derived from the endpoint images of the last
+                 fusion: str = "midpoint", Wi_list=None, keep_x: bool = False, derive_z: bool | None = None,
+                 ray_weights=None):
+        """``ray_weights``: per-ray weights omega of the data term 1/2 sum_r omega_r (A x - b)_r^2
+        (node_ray_weights: None, one array for every node, or a per-global-node sequence; finite,
+        >= 0, checked once here on the host; a node without an entry has omega = 1).  None leaves
+        the unweighted path untouched.
+
+        ``derive_z``: z_ij is not stored but derived from the endpoint images of the last
         consensus (``x_prev``, one row per x_ext row; ABI 7; midpoint fusion only).  None: the
         edge-state rule (plan.z_is_stored) on this batch alone -- stored z, the faster form,
         unless its rows would exceed the rule's share of HBM; RankGroups passes the run's one
@@ -61,6 +83,9 @@ class NodeBatch:
         V = plan.V
         if V < 1:
             raise ValueError("rank owns no graph nodes")
+        wts = node_ray_weights(ray_weights, plan.local_nodes, m)
+        if wts is not None and hasattr(geom, "create_ctx"):
+            raise ValueError(CSR_WEIGHTS_MSG)
         sdt = torch.float64 if dtype == "float64" else torch.float32
         self.ctx = _Ctx(geom, dtype, device, max_images=max(1, V))
         self.x_ext = torch.zeros((plan.n_xext, n), dtype=torch.float64, device=dev)
@@ -149,9 +174,46 @@ class NodeBatch:
             _lib.ADMM_FUSE_WEIGHTED if fusion == "weighted" else _lib.ADMM_FUSE_MIDPOINT,
             _lib.ADMM_BATCH_KEEP_X if keep_x else 0,
             p(self.y_b), p(self.w), p(self.x_prev))
+        # per-ray weights [V][m] in the sample dtype (None: the unweighted batch, no buffer, no call)
+        self.ray_weights = self._weights_tensor(wts)
         torch.cuda.synchronize(dev)
         _lib.check(self.lib.admm_batch_bind(self.ctx.h, C.byref(self.cb)), "admm_batch_bind")
+        self._apply_ray_weights()
         _lib.check(self.lib.admm_batch_atb(self.ctx.h, p(self.atb), C.c_void_p(self._s())),
+                   "admm_batch_atb")
+
+    def _weights_tensor(self, wts):
+        """{g: (m,)} host weights -> the batch's [V][m] device tensor (1 where a node has none)."""
+        if wts is None:
+            return None
+        t = torch.ones_like(self.b)
+        for k, g in enumerate(self.plan.local_nodes):
+            if g in wts:
+                t[k].copy_(torch.as_tensor(wts[g]).to(device=self.dev, dtype=t.dtype))
+        return t
+
+    def _apply_ray_weights(self) -> None:
+        """After every bind (which drops them): the batch's weights, if it has any."""
+        if self.ray_weights is not None:
+            _lib.check(self.lib.admm_batch_set_ray_weights(self.ctx.h, C.c_void_p(self.ray_weights.data_ptr()),
+                                                           C.c_void_p(self._s())), "admm_batch_set_ray_weights")
+
+    def set_ray_weights(self, ray_weights) -> None:
+        """New per-ray weights for the bound batch (as at construction; None clears them): the
+        library re-records its sequences and A^T (omega b) is formed again."""
+        wts = node_ray_weights(ray_weights, self.plan.local_nodes, self.geom.m)
+        if wts is not None and hasattr(self.geom, "create_ctx"):
+            raise ValueError(CSR_WEIGHTS_MSG)
+        if wts is None and self.ray_weights is None:
+            return
+        self.ray_weights = self._weights_tensor(wts)
+        torch.cuda.synchronize(self.dev)
+        if wts is None:
+            _lib.check(self.lib.admm_batch_set_ray_weights(self.ctx.h, C.c_void_p(0), C.c_void_p(self._s())),
+                       "admm_batch_set_ray_weights")
+        else:
+            self._apply_ray_weights()
+        _lib.check(self.lib.admm_batch_atb(self.ctx.h, C.c_void_p(self.atb.data_ptr()), C.c_void_p(self._s())),
                    "admm_batch_atb")
 
     def set_precisions(self, qs) -> None:
@@ -169,6 +231,7 @@ class NodeBatch:
                 self.dsum[k] += self.q[self.inc_qslot_host[s]]
         torch.cuda.synchronize(self.dev)
         _lib.check(self.lib.admm_batch_bind(self.ctx.h, C.byref(self.cb)), "admm_batch_bind")
+        self._apply_ray_weights()
 
     def set_local_images(self, images) -> None:
         """Local rows of x_ext <- ``images[g]`` (float64 (n,) device tensors by global node)."""

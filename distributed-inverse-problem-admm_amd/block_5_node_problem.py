@@ -42,7 +42,7 @@ import torch
 
 from admm_hip import _lib
 from admm_hip.admm import DEFAULT_MU_FACTOR
-from admm_hip.geometry import RayTransform
+from admm_hip.geometry import CSR_WEIGHTS_MSG, RayTransform, ray_weights_host
 from admm_hip.matrix import MatrixOperator, as_operators
 from admm_hip.plan import ShardPlan
 from admm_hip.solver import NodeBatch
@@ -111,11 +111,17 @@ def _operator(Ai, N):
 
 
 class _Problem:
-    def __init__(self, Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms, xi):
+    def __init__(self, Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms, xi, ray_weights=None):
         if len(neighbor_terms) != len(Qij_terms):
             raise ValueError("neighbor_terms and Qij_terms differ in length")
         if isinstance(Ai, (RayTransform, MatrixOperator)):
             _operator(Ai, N)  # (validated now; a matrix is converted on a cache miss only)
+        # per-ray weights of the data term (checked here, on the host); None: the reference's problem
+        self.w = None
+        if ray_weights is not None:
+            if not isinstance(Ai, RayTransform):
+                raise ValueError(CSR_WEIGHTS_MSG)
+            self.w = ray_weights_host(ray_weights, Ai.shape[0])
         self.A0, self.b, self.rho, self.N, self.lam = Ai, bi, float(rho), N, float(lam_tv)
         self.v = list(neighbor_terms)
         self.q = list(Qij_terms)
@@ -129,7 +135,8 @@ class _Problem:
     def _key(self, cfg):
         b = self.b.detach().to("cpu").numpy() if isinstance(self.b, torch.Tensor) else np.asarray(self.b)
         bd = hashlib.blake2b(np.ascontiguousarray(b).tobytes(), digest_size=16).hexdigest()
-        return (id(self.A0), bd, str(b.dtype), len(self.v), cfg, self.rho, self.lam, self.N)
+        wd = None if self.w is None else hashlib.blake2b(self.w.tobytes(), digest_size=16).hexdigest()
+        return (id(self.A0), bd, str(b.dtype), len(self.v), cfg, self.rho, self.lam, self.N, wd)
 
     def _build(self, cfg, qhost):
         tv_iters, cg_iters, mu, tv_kind = cfg
@@ -138,7 +145,8 @@ class _Problem:
         qfn.qslot_key = lambda i, j: ("nbr", j)  # one slot per neighbour: set_precisions rewrites them
         return NodeBatch(A.geom, A.dtype, _star_plan(len(self.v)), [self.b], qfn, self.rho, self.lam, mu,
                          tv_iters, cg_iters, tv_kind, None, A.device,
-                         derive_z=False)  # the targets v_ij are the caller's: stored as z, y = 0
+                         derive_z=False,  # the targets v_ij are the caller's: stored as z, y = 0
+                         ray_weights=None if self.w is None else [self.w])
 
     def _acquire(self, cfg, warm):
         n = self.N * self.N
@@ -192,8 +200,10 @@ class _Problem:
         return self.value
 
 
-def build_node_problem(Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms):
-    """(xi, prob) for node objective eq.(1) -- block_5_node_problem.py:6-32."""
+def build_node_problem(Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms, ray_weights=None):
+    """(xi, prob) for node objective eq.(1) -- block_5_node_problem.py:6-32.  ``ray_weights``
+    (an (m,) or (angles, det) array, finite, >= 0): the data term becomes
+    1/2 sum_r w_r (A x - b)_r^2 (geometry operators only)."""
     xi = _Variable(Ai.shape[1])
-    prob = _Problem(Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms, xi)
+    prob = _Problem(Ai, bi, rho, neighbor_terms, N, lam_tv, Qij_terms, xi, ray_weights)
     return xi, prob

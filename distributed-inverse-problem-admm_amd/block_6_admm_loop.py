@@ -45,7 +45,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_acceleration=1, scs_lookback=10, scs_scale=1e-1,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
-                       phantom_true=None, write_params=True):
+                       phantom_true=None, write_params=True, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
     cg = int(cg_iters)
     total = int(tv_iters) if tv_iters is not None else _rounds(scs_total_iters, cg)
@@ -59,7 +59,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        cg_iters=cg, tv_kind=tv_kind, group=group, write_params=write_params,
                        inner_chunks=chunks,
                        chunk_snapshot_dir=scs_snapshot_dir if chunks is not None else None,
-                       chunk_save_every=scs_save_every_chunks)
+                       chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

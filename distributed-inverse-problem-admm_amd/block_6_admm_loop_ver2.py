@@ -27,6 +27,10 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
 * ``data_range``    L of PSNR and SSIM (default phantom_true.max() - phantom_true.min())
 * ``metrics_mask``  (N, N) or (n,) mask of the pixels the metrics count (default: all)
 
+* ``ray_weights``   per-ray weights of the data term, 1/2 sum_r w_r (A x - b)_r^2: None, one
+                (angles, det) / (m,) array for every node, or one entry (array or None) per node;
+                finite and >= 0, 0 masks a ray (geometry operators only)
+
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
 from __future__ import annotations
@@ -43,7 +47,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
                        max_inner_updates=10, x_init=None, metrics=None, data_range=None,
-                       metrics_mask=None):
+                       metrics_mask=None, ray_weights=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
     del max_inner_iters  # accepted but unused, as in the reference (_ver2:17)
     return run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=lam_tv, rho=rho,
@@ -53,4 +57,4 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     tv_iters=tv_iters, cg_iters=cg_iters, tv_kind=tv_kind, group=group,
                     write_params=write_params, fusion=fusion, inner_tol=inner_tol,
                     max_inner_updates=max_inner_updates, x_init=x_init, metrics=metrics,
-                    data_range=data_range, metrics_mask=metrics_mask)
+                    data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights)

@@ -156,6 +156,10 @@ struct admm_ctx {
   admm_ctx* half = nullptr;
   Buf xs, xsT, p, pT, Hp, sino, bI, fpart, r, c, d2, e2;
   Buf dsumS;  // rho D, D = sum_j q_ij, as interleaved samples (BACK_H epilogue)
+  // per-ray weights omega of the bound batch (admm_batch_set_ray_weights), packed into the layout
+  // of the sinogram scratch they multiply ([chunk][ray][vb], 0 in the lanes without a node)
+  Buf wS;
+  bool weighted = false;
   Buf x2, p2; // ping-pong partners of x (local rows) and p for the fused TV update
   Buf pring;  // CG direction slots 1 .. K-1 (direction ring; slot 0 = p, slot K = p2)
   Buf ats;    // A^T (A xs - b) of the last update's final x (ADMM_BATCH_KEEP_X)
@@ -426,8 +430,10 @@ int bind_fwd_plan(admm_ctx* C, int V) {
   return ADMM_OK;
 }
 
+// wts: the bound batch's packed per-ray weights (the weighted instantiations) or null
 template <typename T, int VB, int MODE>
-int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, double* part, int V, hipStream_t s) {
+int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, double* part, int V, hipStream_t s,
+               const T* wts = nullptr) {
   if (C->csr) {  // explicit matrix: one thread per sinogram row
     dim3 cg((C->mrays + kBlock - 1) / kBlock, (V + VB - 1) / VB);
     hipLaunchKernelGGL((k_csr_fwd<T, VB, MODE>), cg, dim3(kBlock), 0, s, (const int*)C->f_ptr.p,
@@ -436,8 +442,12 @@ int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, do
     return ADMM_OK;
   }
   dim3 grid((C->g.n_det + kFwdRays - 1) / kFwdRays, C->g.n_angles, (V + VB - 1) / VB);
-  hipLaunchKernelGGL((k_fwd<T, VB, MODE>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang, C->g.N,
-                     C->g.n_det, C->g.n_angles, V);
+  if (wts)
+    hipLaunchKernelGGL((k_fwd<T, VB, MODE, const T*>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang,
+                       C->g.N, C->g.n_det, C->g.n_angles, V, wts);
+  else
+    hipLaunchKernelGGL((k_fwd<T, VB, MODE>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang, C->g.N,
+                       C->g.n_det, C->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
 }
@@ -491,8 +501,9 @@ int launch_fwd_batch(admm_ctx* C, const T* img, const T* imgT, T* sino, const T*
     C->tf_next += 2;
     HIPCHK(hipEventRecord(ev[0], s));
   }
+  const T* wts = C->weighted ? (const T*)C->wS.p : nullptr;
   if (C->n_groups == 0) {
-    RET((launch_fwd<T, VB, MODE>(C, img, imgT, sino, b, part, V, s)));
+    RET((launch_fwd<T, VB, MODE>(C, img, imgT, sino, b, part, V, s, wts)));
     if (ev) HIPCHK(hipEventRecord(ev[1], s));
     return ADMM_OK;
   }
@@ -505,14 +516,22 @@ int launch_fwd_batch(admm_ctx* C, const T* img, const T* imgT, T* sino, const T*
     // MODE 0: two threads per virtual ray (k_fwd_combine_mirror); MODE 1: one (its block partials)
     const size_t mthreads = (size_t)mh * (MODE == 0 ? 2 : 1);
     dim3 mg((unsigned)((mthreads + kBlock - 1) / kBlock), nch * (VB / MH));
-    hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE>), mg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino,
-                       b, part, C->half->fang, C->g.n_det, C->half->g.n_angles, V);
+    if (wts)
+      hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE, const T*>), mg, dim3(kBlock), 0, s,
+                         (const T*)C->fpart.p, sino, b, part, C->half->fang, C->g.n_det, C->half->g.n_angles, V, wts);
+    else
+      hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE>), mg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino,
+                         b, part, C->half->fang, C->g.n_det, C->half->g.n_angles, V);
     CHECK_LAUNCH();
     return ADMM_OK;
   }
   dim3 cg((C->mrays + kBlock - 1) / kBlock, nch);
-  hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
-                     C->fang, C->g.n_det, C->g.n_angles, V);
+  if (wts)
+    hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE, const T*>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
+                       C->fang, C->g.n_det, C->g.n_angles, V, wts);
+  else
+    hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
+                       C->fang, C->g.n_det, C->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
 }
@@ -565,7 +584,8 @@ int launch_back(admm_ctx* C, BackArgs<T> a, int V, hipStream_t s) {
   a.n_ang = C->g.n_angles;
   a.V = V;
   const int N = C->g.N;
-  dim3 grid((N + kBTJ - 1) / kBTJ, (N + kBTI - 1) / kBTI, MODE == BACK_WSQ ? 1 : (V + VB - 1) / VB);
+  constexpr bool kOneImage = MODE == BACK_WSQ || MODE == BACK_WSQW;  // the column norms: no node chunks
+  dim3 grid((N + kBTJ - 1) / kBTJ, (N + kBTI - 1) / kBTI, kOneImage ? 1 : (V + VB - 1) / VB);
   if (C->csr) {
     a.csr_ptr = (const int*)C->t_ptr.p;
     a.csr_idx = (const int*)C->t_idx.p;
@@ -889,6 +909,28 @@ int capture(admm_ctx* C, F&& fn, hipGraph_t* g, hipGraphExec_t* x) {
   if (e != hipSuccess) return fail(ADMM_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
   HIPCHK(hipGraphInstantiate(x, graph, nullptr, nullptr, 0));
   *g = graph;
+  return ADMM_OK;
+}
+
+// the bound batch's x-update and consensus sequences, recorded once and replayed every iteration
+// (admm_batch_bind; again by admm_batch_set_ray_weights, whose launches differ)
+int record_graphs(admm_ctx* C) {
+  RET(free_graphs(C));
+  auto fu = [&](hipStream_t s) {
+    return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s) : enqueue_update_any<double>(C, s);
+  };
+  RET(capture(C, fu, &C->g_update, &C->x_update));
+  if (C->b.flags & ADMM_BATCH_KEEP_X) {
+    auto fr = [&](hipStream_t s) {
+      return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s, true)
+                                        : enqueue_update_any<double>(C, s, true);
+    };
+    RET(capture(C, fr, &C->g_update_reuse, &C->x_update_reuse));
+  }
+  if (C->b.n_edges > 0) {
+    auto fc = [&](hipStream_t s) { return enqueue_consensus(C, s); };
+    RET(capture(C, fc, &C->g_cons, &C->x_cons));
+  }
   return ADMM_OK;
 }
 
@@ -1344,7 +1386,7 @@ int admm_ctx_destroy(admm_ctx* C) {
   C->half = nullptr;
   Buf* bufs[] = {&C->op_img, &C->op_imgT, &C->op_sino, &C->op_fpart, &C->xs, &C->xsT, &C->p, &C->pT, &C->Hp, &C->sino, &C->bI, &C->fpart, &C->r, &C->c,
                  &C->d2, &C->e2, &C->partH, &C->partS, &C->partD, &C->partE, &C->redH, &C->fg_order, &C->dsumS, &C->ats,
-                 &C->f_ptr, &C->f_idx, &C->f_val, &C->t_ptr, &C->t_idx, &C->t_val, &C->x2, &C->p2, &C->pring};
+                 &C->f_ptr, &C->f_idx, &C->f_val, &C->t_ptr, &C->t_idx, &C->t_val, &C->x2, &C->p2, &C->pring, &C->wS};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (Buf& b : C->op_order)
@@ -1401,6 +1443,25 @@ int admm_column_norms_sq(admm_ctx* C, double* W, void* stream) {
   return launch_back<double, 1, BACK_WSQ>(C, a, 1, s);
 }
 
+int admm_column_norms_sq_weighted(admm_ctx* C, const void* w, double* W, void* stream) {
+  if (!C || !w || !W) return fail(ADMM_E_INVALID, "null argument");
+  if (C->csr)
+    return fail(ADMM_E_INVALID, "weighted column norms are not supported for explicit-matrix contexts: scale "
+                                "the rows of A by sqrt(omega) instead (exact there)");
+  DEVICE_SCOPE(C->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (C->dtype == ADMM_DTYPE_F32) {
+    BackArgs<float> a{};
+    a.sino = (const float*)w;
+    a.out_d = W;
+    return launch_back<float, 1, BACK_WSQW>(C, a, 1, s);
+  }
+  BackArgs<double> a{};
+  a.sino = (const double*)w;
+  a.out_d = W;
+  return launch_back<double, 1, BACK_WSQW>(C, a, 1, s);
+}
+
 int admm_tv_grad(admm_ctx* C, const double* x, double* gx, double* gy, int nimg, void* stream) {
   if (!C || !x || !gx || !gy || nimg < 1) return fail(ADMM_E_INVALID, "bad argument");
   DEVICE_SCOPE(C->device);
@@ -1450,6 +1511,7 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
   HIPCHK(hipDeviceSynchronize());
   RET(free_graphs(C));
   C->b = B;
+  C->weighted = false;  // a bind drops the per-ray weights (admm_batch_set_ray_weights)
   const int V = B.V;
   C->vb = vb_for(V, C->dtype);
   RET(bind_fwd_plan(C, V));
@@ -1506,22 +1568,41 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
     return ADMM_OK;
   }));
   HIPCHK(hipStreamSynchronize(C->cap));
-  // the x-update and consensus sequences, recorded once and replayed every iteration
-  auto fu = [&](hipStream_t s) {
-    return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s) : enqueue_update_any<double>(C, s);
-  };
-  RET(capture(C, fu, &C->g_update, &C->x_update));
-  if (B.flags & ADMM_BATCH_KEEP_X) {
-    auto fr = [&](hipStream_t s) {
-      return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s, true)
-                                        : enqueue_update_any<double>(C, s, true);
-    };
-    RET(capture(C, fr, &C->g_update_reuse, &C->x_update_reuse));
+  RET(record_graphs(C));
+  HIPCHK(hipDeviceSynchronize());
+  return ADMM_OK;
+}
+
+int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
+  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
+  if (C->csr)
+    return fail(ADMM_E_INVALID, "per-ray weights are not supported for explicit-matrix contexts: scale the "
+                                "rows of A and b by sqrt(omega) instead (exact there)");
+  DEVICE_SCOPE(C->device);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipDeviceSynchronize());
+  if (!w && !C->weighted) return ADMM_OK;
+  C->weighted = false;
+  C->ats_valid = false;  // the kept A^T s belongs to the previous weights
+  if (w) {
+    const int V = C->b.V, m = C->mrays;
+    const size_t Vp = (size_t)((V + C->vb - 1) / C->vb) * C->vb;
+    RET(ensure(C->wS, Vp * m * dsize(C->dtype)));
+    RET(with_vb(C->vb, [&](auto vbc) {
+      constexpr int VB = decltype(vbc)::value;
+      const dim3 grid((m + 255) / 256, (V + VB - 1) / VB);
+      if (C->dtype == ADMM_DTYPE_F32)
+        hipLaunchKernelGGL((k_pack<float, VB>), grid, dim3(256), 0, s, (const float*)w, (float*)C->wS.p, m, V);
+      else
+        hipLaunchKernelGGL((k_pack<double, VB>), grid, dim3(256), 0, s, (const double*)w, (double*)C->wS.p, m, V);
+      CHECK_LAUNCH();
+      return ADMM_OK;
+    }));
+    HIPCHK(hipStreamSynchronize(s));
+    C->weighted = true;
   }
-  if (B.n_edges > 0) {
-    auto fc = [&](hipStream_t s) { return enqueue_consensus(C, s); };
-    RET(capture(C, fc, &C->g_cons, &C->x_cons));
-  }
+  RET(record_graphs(C));
   HIPCHK(hipDeviceSynchronize());
   return ADMM_OK;
 }
@@ -1533,8 +1614,12 @@ int batch_atb(admm_ctx* C, double* atb_out, hipStream_t s) {
   return with_vb(C->vb, [&](auto vbc) {
     constexpr int VB = decltype(vbc)::value;
     const int nch = (V + VB - 1) / VB;
-    hipLaunchKernelGGL((k_pack<T, VB>), dim3((C->mrays + 255) / 256, nch), dim3(256), 0, s, (const T*)C->b.b,
-                       (T*)C->bI.p, C->mrays, V);
+    if (C->weighted)  // A^T (omega b)
+      hipLaunchKernelGGL((k_pack_w<T, VB>), dim3((C->mrays + 255) / 256, nch), dim3(256), 0, s, (const T*)C->b.b,
+                         (const T*)C->wS.p, (T*)C->bI.p, C->mrays, V);
+    else
+      hipLaunchKernelGGL((k_pack<T, VB>), dim3((C->mrays + 255) / 256, nch), dim3(256), 0, s, (const T*)C->b.b,
+                         (T*)C->bI.p, C->mrays, V);
     CHECK_LAUNCH();
     BackArgs<T> a{};
     a.sino = (const T*)C->bI.p;
@@ -1642,7 +1727,8 @@ int time_fwd(admm_ctx* C, int reps, int in_solve, hipStream_t s, float* ms) {
     // the forward tap kernel alone, back to back: k_fwdg (every sample tap) when grouped, else k_fwd
     auto one = [&]() -> int {
       if (C->n_groups > 0) return launch_fwdg_taps<T, VB>(C, (T*)C->xs.p, (T*)C->xsT.p, C->b.V, s);
-      return launch_fwd<T, VB, 0>(C, (T*)C->xs.p, (T*)C->xsT.p, (T*)C->sino.p, nullptr, nullptr, C->b.V, s);
+      return launch_fwd<T, VB, 0>(C, (T*)C->xs.p, (T*)C->xsT.p, (T*)C->sino.p, nullptr, nullptr, C->b.V, s,
+                                  C->weighted ? (const T*)C->wS.p : nullptr);
     };
     RET(one());
     hipEvent_t e0, e1;

@@ -469,11 +469,24 @@ __device__ __forceinline__ void block_reduce_flat(const double (&vals)[NT], doub
 // MODE 0: store A x (interleaved).
 // MODE 1: store s = A x - b (interleaved; b node-major [V][m]) and partials of ||s||^2.
 // ===========================================================================
-template <typename T, int VB, int MODE>
+// Per-ray weights (admm_batch_set_ray_weights): wts holds omega in the layout of sino,
+// [chunk][ray][VB] with 0 in the lanes that have no node, read at the address the thread stores to.
+// MODE 0: sino = (A x) * omega (L first, then omega, each one rounding in T).  MODE 1: r = A x - b,
+// the stored s = omega * r and the partials omega * r^2.  With omega = 1 every product is exact.
+// The weighted form is the instantiation with one trailing kernel argument, W = const T* (the
+// unweighted one, W empty, keeps its signature and its code).
+template <typename T>
+__device__ __forceinline__ const T* wt_ptr() { return nullptr; }
+template <typename T>
+__device__ __forceinline__ const T* wt_ptr(const T* w) { return w; }
+
+template <typename T, int VB, int MODE, typename... W>
 __global__ __launch_bounds__(kFwdBlock) void k_fwd(const T* __restrict__ img, const T* __restrict__ imgT,
                                                 T* __restrict__ sino, const T* __restrict__ bsino,
                                                 double* __restrict__ part, const FwdAngle* __restrict__ ang,
-                                                int N, int n_det, int n_ang, int V) {
+                                                int N, int n_det, int n_ang, int V, W... wp) {
+  constexpr bool WT = sizeof...(W) > 0;
+  const T* __restrict__ wts = wt_ptr<T>(wp...);
   const int lane = threadIdx.x & 63;
   const int seg = threadIdx.x >> 6;
   const int k = blockIdx.x * kFwdRays + lane;
@@ -554,7 +567,8 @@ __global__ __launch_bounds__(kFwdBlock) void k_fwd(const T* __restrict__ img, co
   for (int u = 0; u < VB; ++u) sq[u] = 0.0;
   if (seg == 0 && k < n_det) {
     const size_t ray = (size_t)t * n_det + k;
-    T s[VB];
+    T s[VB], w[VB];
+    if constexpr (WT) gload<T, VB>(wts + ((size_t)chunk * n_ang * n_det + ray) * VB, w);
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
       s[u] = (((red[0][u][lane] + red[1][u][lane]) + (red[2][u][lane] + red[3][u][lane])) +
@@ -564,9 +578,15 @@ __global__ __launch_bounds__(kFwdBlock) void k_fwd(const T* __restrict__ img, co
         if (u < nv) {
           s[u] = s[u] - bsino[(size_t)(v0 + u) * n_ang * n_det + ray];
           sq[u] = (double)s[u] * (double)s[u];
+          if constexpr (WT) {
+            sq[u] = (double)w[u] * sq[u];
+            s[u] = w[u] * s[u];
+          }
         } else {
           s[u] = T(0);
         }
+      } else if constexpr (WT) {
+        s[u] = s[u] * w[u];
       }
     }
     gstore<T, VB>(sino + ((size_t)chunk * n_ang * n_det + ray) * VB, s);
@@ -1203,11 +1223,14 @@ __global__ __launch_bounds__(kFgThreads) __attribute__((amdgpu_waves_per_eu(CPB 
 
 // Sum the kFgSeg segment partials in fixed order, scale by L(t):
 // MODE 0: sino = A x.  MODE 1: s = A x - b (b node-major) + per-block partials of ||s||^2.
-template <typename T, int VB, int MODE>
+// W = const T*: per-ray weights in the layout of sino (see k_fwd).
+template <typename T, int VB, int MODE, typename... W>
 __global__ __launch_bounds__(kBlock) void k_fwd_combine(const T* __restrict__ part, T* __restrict__ sino,
                                                         const T* __restrict__ bsino, double* __restrict__ pout,
                                                         const FwdAngle* __restrict__ ang, int n_det, int n_ang,
-                                                        int V) {
+                                                        int V, W... wp) {
+  constexpr bool WT = sizeof...(W) > 0;
+  const T* __restrict__ wts = wt_ptr<T>(wp...);
   const int chunk = blockIdx.y, v0 = chunk * VB, nv = min(VB, V - v0);
   const int nch = (V + VB - 1) / VB;
   const size_t m_rays = (size_t)n_ang * n_det;
@@ -1217,7 +1240,8 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine(const T* __restrict__ pa
   for (int u = 0; u < VB; ++u) sq[u] = 0.0;
   if (ray < m_rays) {
     const T L = (T)ang[ray / n_det].L * kFgWScale<T>;
-    T acc[VB], pv[VB];
+    T acc[VB], pv[VB], w[VB];
+    if constexpr (WT) gload<T, VB>(wts + ((size_t)chunk * m_rays + ray) * VB, w);
     gload<T, VB>(part + ((size_t)chunk * m_rays + ray) * VB, acc);
 #pragma unroll
     for (int sg = 1; sg < kFgSeg; ++sg) {
@@ -1232,9 +1256,15 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine(const T* __restrict__ pa
         if (u < nv) {
           acc[u] -= bsino[(size_t)(v0 + u) * m_rays + ray];
           sq[u] = (double)acc[u] * (double)acc[u];
+          if constexpr (WT) {
+            sq[u] = (double)w[u] * sq[u];
+            acc[u] = w[u] * acc[u];
+          }
         } else {
           acc[u] = T(0);
         }
+      } else if constexpr (WT) {
+        acc[u] *= w[u];
       }
     }
     gstore<T, VB>(sino + ((size_t)chunk * m_rays + ray) * VB, acc);
@@ -1255,12 +1285,16 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine(const T* __restrict__ pa
 // c' % MS: lanes u < VB/2 are angle t, lanes u >= VB/2 angle a-1-t (pi - theta_t) of the same
 // real nodes.  MODE 1: s = A x - b against the real node-major b, and per real node one
 // ||s||^2 partial per block holding both of its angles' residuals (summed in a fixed order).
-template <typename T, int VB, int VBR, int MODE>
+// W = const T*: per-ray weights in the layout of the real sinogram; each half reads the weights of
+// the angle it stores to (the hi half those of angle a-1-t).
+template <typename T, int VB, int VBR, int MODE, typename... W>
 __global__ __launch_bounds__(kBlock) void k_fwd_combine_mirror(const T* __restrict__ part, T* __restrict__ sino,
                                                                const T* __restrict__ bsino,
                                                                double* __restrict__ pout,
                                                                const FwdAngle* __restrict__ ang, int n_det,
-                                                               int n_ang_half, int V) {
+                                                               int n_ang_half, int V, W... wp) {
+  constexpr bool WT = sizeof...(W) > 0;
+  const T* __restrict__ wts = wt_ptr<T>(wp...);
   constexpr int MH = VB / 2, MS = VBR / MH;
   const int chunk = blockIdx.y, nch = gridDim.y;  // virtual chunks
   const int rc = chunk / MS, mq = chunk % MS;     // real chunk, lane block
@@ -1287,6 +1321,12 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine_mirror(const T* __restri
 #pragma unroll
     for (int u = 0; u < MH; ++u) acc[u] *= L;
     const size_t dst = h ? (size_t)(2 * n_ang_half - 1 - t) * n_det + k : ray;
+    if constexpr (WT) {
+      T w[MH];
+      gload<T, MH>(wts + (size_t)rc * m_full * VBR + mq * MH + dst * VBR, w);
+#pragma unroll
+      for (int u = 0; u < MH; ++u) acc[u] *= w[u];
+    }
     gstore<T, MH>(sino + (size_t)rc * m_full * VBR + mq * MH + dst * VBR, acc);
     return;
   }
@@ -1306,7 +1346,12 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine_mirror(const T* __restri
 #pragma unroll
       for (int u = 0; u < VB; ++u) acc[u] += pv[u];
     }
-    T lo[MH], hi[MH];
+    T lo[MH], hi[MH], wl[MH], wh[MH];
+    if constexpr (WT) {
+      const T* wbase = wts + (size_t)rc * m_full * VBR + mq * MH;
+      gload<T, MH>(wbase + ray * VBR, wl);
+      gload<T, MH>(wbase + ray2 * VBR, wh);
+    }
 #pragma unroll
     for (int u = 0; u < MH; ++u) {
       lo[u] = acc[u] * L;
@@ -1315,11 +1360,20 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine_mirror(const T* __restri
         if (vr0 + u < V) {
           lo[u] -= bsino[(size_t)(vr0 + u) * m_full + ray];
           hi[u] -= bsino[(size_t)(vr0 + u) * m_full + ray2];
-          sq[u] = (double)lo[u] * (double)lo[u] + (double)hi[u] * (double)hi[u];
+          if constexpr (WT) {
+            sq[u] = (double)wl[u] * ((double)lo[u] * (double)lo[u]) + (double)wh[u] * ((double)hi[u] * (double)hi[u]);
+            lo[u] = wl[u] * lo[u];
+            hi[u] = wh[u] * hi[u];
+          } else {
+            sq[u] = (double)lo[u] * (double)lo[u] + (double)hi[u] * (double)hi[u];
+          }
         } else {
           lo[u] = T(0);
           hi[u] = T(0);
         }
+      } else if constexpr (WT) {
+        lo[u] *= wl[u];
+        hi[u] *= wh[u];
       }
     }
     T* base = sino + (size_t)rc * m_full * VBR + mq * MH;  // (MH-lane blocks: aligned vector stores)
@@ -1346,6 +1400,8 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine_mirror(const T* __restri
 //   BACK_PLAIN : out = A^T s  (interleaved samples)                  (operator API)
 //   BACK_ATB   : atb = A^T b (float64 node-major)                    (setup)
 //   BACK_WSQ   : W = max(sum_r A[r,p]^2, 1e-12) (float64)            (make_precisions, block_3:20-23)
+//   BACK_WSQW  : W = max(sum_r omega_r A[r,p]^2, 1e-12) (float64); omega is `sino` (one node), staged in
+//                the windows of BACK_PLAIN, each tap fma(w, w * omega, acc): omega = 1 gives BACK_WSQ's bits
 //   BACK_H     : Hp = A^T A p + rho D p + mu K^T K p; partials p.Hp, r.Hp, Hp.Hp, r.r, r.p (CG)
 //   BACK_INIT  : r = A^T b + rho c + mu K^T(d-e) - H xs;  p = r                      (CG start)
 //   BACK_DIAG  : g = A^T s + rho (D x - c) + lam K^T sub(Kx); partials |g|^2, TV(x),
@@ -1365,7 +1421,7 @@ struct EdgeIn {
   const int* eb;
 };
 
-enum BackMode { BACK_PLAIN = 0, BACK_ATB = 1, BACK_WSQ = 2, BACK_H = 3, BACK_INIT = 4, BACK_DIAG = 5 };
+enum BackMode { BACK_PLAIN = 0, BACK_ATB = 1, BACK_WSQ = 2, BACK_H = 3, BACK_INIT = 4, BACK_DIAG = 5, BACK_WSQW = 6 };
 
 template <typename T>
 struct BackArgs {
@@ -1489,7 +1545,7 @@ __device__ __forceinline__ void back_epilogue(const BackArgs<T>& A, int i, int j
 #pragma unroll
     for (int u = 0; u < VB; ++u)
       if (u < nv) A.out_d[(size_t)(v0 + u) * npix + pix] = (double)acc[u];
-  } else if constexpr (MODE == BACK_WSQ) {
+  } else if constexpr (MODE == BACK_WSQ || MODE == BACK_WSQW) {
     A.out_d[pix] = fmax((double)acc[0], 1e-12);
   } else if constexpr (MODE == BACK_H && std::is_same<T, float>::value) {
     // float32 samples: H p = acc + rho D p + mu K^T K p formed in float32 (p, D and the taps'
@@ -1862,6 +1918,10 @@ void k_back(BackArgs<T> A) {
     if constexpr (MODE == BACK_WSQ) {
       acc[0] = fma(w0, w0, acc[0]);
       acc[0] = fma(w1, w1, acc[0]);
+    } else if constexpr (MODE == BACK_WSQW) {
+      static_assert(MODE != BACK_WSQW || VB == 1, "one weight sinogram");
+      acc[0] = fma(w0, w0 * s0[0].v[0], acc[0]);
+      acc[0] = fma(w1, w1 * s1[0].v[0], acc[0]);
     } else {
 #pragma unroll
       for (int q = 0; q < NPL; ++q)
@@ -1879,7 +1939,7 @@ void k_back(BackArgs<T> A) {
   // 4 waves/SIMD); kmin is double-buffered.  Otherwise: compute kmin, stage, tap per chunk.
   // (float samples, H/INIT modes: the float64 and DIAG variants would spill)
   constexpr bool PF = (std::is_same<T, float>::value || NPL <= 2) && (MODE == BACK_H || MODE == BACK_INIT ||
-                                                                     MODE == BACK_PLAIN || MODE == BACK_ATB);
+                                                                     MODE == BACK_PLAIN || MODE == BACK_ATB || MODE == BACK_WSQW);
   constexpr int SPER = (ANGC * kBWin * NPL + kBkThreads - 1) / kBkThreads;
   Pack<T, PV> wst[SPER];
   // a chunk's window offsets from its angle records; the record load (kmin_load) is split from
@@ -2018,7 +2078,7 @@ void k_back(BackArgs<T> A) {
 
   if constexpr (std::is_same<T, float>::value && !CSR) {
     if (A.wexp != 0) {  // undo the weight scaling (a power of two: exact)
-      const int e = (MODE == BACK_WSQ) ? 2 * A.wexp : A.wexp;
+      const int e = (MODE == BACK_WSQ || MODE == BACK_WSQW) ? 2 * A.wexp : A.wexp;
 #pragma unroll
       for (int u = 0; u < VB; ++u) acc[u] = ldexpf(acc[u], e);
     }
@@ -3054,6 +3114,20 @@ __global__ void k_pack(const T* __restrict__ in, T* __restrict__ out, int L, int
   T s[VB];
 #pragma unroll
   for (int u = 0; u < VB; ++u) s[u] = (v0 + u < V) ? in[(size_t)(v0 + u) * L + q] : T(0);
+  gstore<T, VB>(out + ((size_t)chunk * L + q) * VB, s);
+}
+
+// k_pack with every sample multiplied by its packed weight (wts: the interleaved layout of out):
+// omega * b for admm_batch_atb under admm_batch_set_ray_weights, the product rounded once in T
+template <typename T, int VB>
+__global__ void k_pack_w(const T* __restrict__ in, const T* __restrict__ wts, T* __restrict__ out, int L, int V) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int chunk = blockIdx.y, v0 = chunk * VB;
+  if (q >= L) return;
+  T s[VB], w[VB];
+  gload<T, VB>(wts + ((size_t)chunk * L + q) * VB, w);
+#pragma unroll
+  for (int u = 0; u < VB; ++u) s[u] = (v0 + u < V) ? w[u] * in[(size_t)(v0 + u) * L + q] : T(0);
   gstore<T, VB>(out + ((size_t)chunk * L + q) * VB, s);
 }
 

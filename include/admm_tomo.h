@@ -67,7 +67,8 @@ extern "C" {
 #define ADMM_BATCH_KEEP_X 1
 
 /* per-node statistics written by admm_node_update (float64) */
-#define ADMM_NODE_STAT_MSE_SINO 0 /* ||A x - b||^2           (block_6_admm_loop_ver2.py:190-194) */
+#define ADMM_NODE_STAT_MSE_SINO 0 /* ||A x - b||^2           (block_6_admm_loop_ver2.py:190-194);
+                                   * with ray weights: sum_r omega_r (A x - b)_r^2 */
 #define ADMM_NODE_STAT_G2 1       /* ||g||^2 stationarity    (block_6_admm_loop_ver2.py:145-149) */
 #define ADMM_NODE_STAT_TV 2       /* TV(x)                   (block_4_tv_helpers.py:5-14) */
 #define ADMM_NODE_STAT_QUAD 3     /* sum_j rho/2 ||x-v_ij||^2_Q (block_5_node_problem.py:26-29) */
@@ -177,6 +178,10 @@ int admm_project_adj(admm_ctx* ctx, const void* sino, void* img, int nimg, void*
 /* W[p] = max(sum_r A[r,p]^2, 1e-12) (float64).  Replaces make_precisions'
  * column sums (block_3_graph_and_precisions.py:20-23, block_1_env_and_imports.py:16-18). */
 int admm_column_norms_sq(admm_ctx* ctx, double* W, void* stream);
+/* W[p] = max(sum_r w_r A[r,p]^2, 1e-12) (float64) for per-ray weights w: [m] in the context dtype
+ * (the precisions of a weighted data term); all-ones w gives admm_column_norms_sq bitwise.  Setup
+ * only.  Explicit-matrix contexts: ADMM_E_INVALID.  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_column_norms_sq_weighted(admm_ctx* ctx, const void* w, double* W, void* stream);
 /* (gx, gy) = K x, forward differences (block_4_tv_helpers.py:17-23), float64. */
 int admm_tv_grad(admm_ctx* ctx, const double* x, double* gx, double* gy, int nimg, void* stream);
 /* out = K^T (px, py), exact adjoint of admm_tv_grad (block_4_tv_helpers.py:25-35). */
@@ -188,8 +193,21 @@ int admm_tv_div(admm_ctx* ctx, const double* px, const double* py, double* out, 
 /* Bind a batch (pointers are captured; the contents may change between calls).
  * Allocates scratch and records the update sequence as a hipGraph.  Synchronous. */
 int admm_batch_bind(admm_ctx* ctx, const admm_batch* batch);
-/* A^T b for the bound batch (setup; writes batch->atb, which is then const). */
+/* A^T b for the bound batch (setup; writes batch->atb, which is then const).  With ray weights
+ * set (admm_batch_set_ray_weights): A^T (omega b), the product rounded once in the context dtype. */
 int admm_batch_atb(admm_ctx* ctx, double* atb_out, void* stream);
+/* Per-ray weights of the bound batch: every node then solves eq.(1) with the data term
+ * 1/2 sum_r omega_r (A x - b)_r^2 (weighted least squares; omega = 0 masks a ray).  w: [V][m] in the
+ * context dtype, finite and >= 0 (the caller's promise), copied into the library's own buffer, packed
+ * in the layout of the sinogram scratch; NULL clears the weights.  The weight is applied where the
+ * forward projection is written (A x -> omega A x, A x - b -> omega (A x - b): no extra launch), so the
+ * back projectors form A^T Omega A; call admm_batch_atb afterwards for A^T Omega b.  Re-records the
+ * batch's sequences; synchronous like admm_batch_bind, which drops the weights (set them again after
+ * every bind).  ADMM_NODE_STAT_MSE_SINO becomes sum_r omega_r (A x - b)_r^2; admm_time_forward /
+ * admm_time_back time the weighted launches.  All-ones weights give bitwise the unweighted results.
+ * Explicit-matrix contexts: ADMM_E_INVALID (scale the rows of A and b by sqrt(omega) there).
+ * Additive: ADMM_ABI_VERSION stays 9. */
+int admm_batch_set_ray_weights(admm_ctx* ctx, const void* w, void* stream);
 /* One x-update of every bound node: neighbour gather v_ij = z_ij - y_ij,i
  * (y_ij,i = y for the lower endpoint, -y or y_b for the higher one),
  * fixed-count split-Bregman/CG solve of eq.(1), diagnostics into node_stats.
