@@ -1,6 +1,7 @@
 // admm_tomo.hip -- C-ABI implementation (include/admm_tomo.h) for MI355X (gfx950).
 //
-// Host side of the hot path: geometry tables, scratch, and the x-update /
+// Host side of the hot path: uploads the planner's tables (fwd_plan.hpp: geometry
+// records and forward plans, plain C++), owns the scratch, and enqueues the x-update /
 // consensus sequences.  A bound batch's sequences are recorded once as
 // hipGraphs and replayed every ADMM iteration (launch-bound at small N
 // otherwise: ~170 kernels per x-update).
@@ -11,15 +12,20 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "../../include/admm_tomo.h"
+#include "fwd_plan.hpp"
 #include "kernels.hpp"
 
 using namespace admm;
+
+// k_fwdg reads the block table the planner fills as int4
+static_assert(sizeof(FgBlock) == sizeof(int4) && alignof(FgBlock) == alignof(int4), "FgBlock must be an int4");
 
 namespace {
 thread_local std::string g_err;
@@ -47,7 +53,9 @@ size_t dsize(int dtype) { return dtype == ADMM_DTYPE_F64 ? 8 : 4; }
 struct DeviceGuard {
   int prev = -1;
   hipError_t err = hipSuccess;
-  explicit DeviceGuard(int device) {
+  DeviceGuard() = default;  // (nothing to restore until enter())
+  explicit DeviceGuard(int device) { enter(device); }
+  void enter(int device) {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     if (prev != device) err = hipSetDevice(device);
   }
@@ -64,16 +72,81 @@ struct DeviceGuard {
   if (_dg.err != hipSuccess)                                                                  \
   return fail(ADMM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_dg.err))
 
-struct Buf {
+#define RET(expr)                   \
+  do {                              \
+    int _rc = (expr);               \
+    if (_rc != ADMM_OK) return _rc; \
+  } while (0)
+
+// The owners below free what they hold when they go (results ignored, as on every teardown
+// path): a context member is released with its context, on every return path of its creation too.
+struct Buf {  // device memory
   void* p = nullptr;
   size_t bytes = 0;
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~Buf() { (void)release(); }
+  hipError_t release() {
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    bytes = 0;
+    return e;
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+struct Graph {  // a recorded sequence: the graph and its executable
+  hipGraph_t g = nullptr;
+  hipGraphExec_t x = nullptr;
+  Graph() = default;
+  Graph(const Graph&) = delete;
+  Graph& operator=(const Graph&) = delete;
+  ~Graph() { reset(); }
+  void reset() {  // both handles go, whatever either destroy returns
+    if (x) (void)hipGraphExecDestroy(x);
+    if (g) (void)hipGraphDestroy(g);
+    x = nullptr;
+    g = nullptr;
+  }
+};
+
+struct Event {  // timing-only event
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  // no system-scope fence (cache writeback / invalidation) at each record, which would
+  // perturb the launches the events bracket
+  int create() {
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+    return ADMM_OK;
+  }
 };
 
 int ensure(Buf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return ADMM_OK;
-  if (b.p) HIPCHK(hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
+  HIPCHK(b.release());
   if (bytes == 0) return ADMM_OK;
   HIPCHK(hipMalloc(&b.p, bytes));
   // hipMemset is enqueued on the null stream, which does not order against non-blocking
@@ -85,6 +158,17 @@ int ensure(Buf& b, size_t bytes) {
   b.bytes = bytes;
   return ADMM_OK;
 }
+
+// ensure + copy of a host table (min_bytes: the allocation of an empty table)
+int upload(Buf& b, const void* src, size_t bytes, size_t min_bytes = 0) {
+  RET(ensure(b, std::max(bytes, min_bytes)));
+  if (bytes > 0) HIPCHK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+  return ADMM_OK;
+}
+template <typename E>
+int upload(Buf& b, const std::vector<E>& v, size_t min_bytes = 0) {
+  return upload(b, v.data(), v.size() * sizeof(E), min_bytes);
+}
 }  // namespace
 
 // error channel shared with the other translation units (masks.hip)
@@ -93,36 +177,35 @@ int fail(int code, const std::string& msg) { return ::fail(code, msg); }
 }  // namespace admm_internal
 
 struct admm_ctx {
+  DeviceGuard scope;  // entered by the destructor only
   admm_geom g{};
   int dtype = ADMM_DTYPE_F32;
   int device = 0;
   int max_images = 0;
   int npix = 0, mrays = 0;
-  FwdAngle* fang = nullptr;
-  BackAngle* bang = nullptr;
-  BackAngleC* bangc = nullptr;
+  Buf fang_b, bang_b, bangc_b;  // the angle records (fwd_plan.hpp GeomTables) on the device
+  const FwdAngle* fang() const { return fang_b.as<const FwdAngle>(); }
+  const BackAngle* bang() const { return bang_b.as<const BackAngle>(); }
+  const BackAngleC* bangc() const { return bangc_b.as<const BackAngleC>(); }
   double Kb = 0.0;  // angle-independent part of the back projector's k_f
   int kbias = 0;    // integer bias making every pixel's k_f positive (k_back)
   int wexp = 0;     // k_back float weights scaled by 2^-wexp (<= 1 for the fma clamp)
-  FgGroup* groups = nullptr;  // angle groups of the grouped forward projector (active plan)
-  FgRange* rng = nullptr;     // its per-block ray ranges
-  int n_groups = 0;           // 0: geometry does not fit the grouped kernel -> k_fwd
-  // the group plans, chosen at bind time: 0: 64-ray chunks, 1: chunks aligned per (row
-  // segment, angle) at the detector centre, 2: chunks aligned per (row segment, chunk);
-  // 3-5: the same with every block's rays clipped to those crossing its segment inside the
-  // image (groups re-planned on the narrower windows)
-  static constexpr int kPlans = 6;
-  FgGroup* plan_groups[kPlans] = {};
-  FgRange* plan_rng[kPlans] = {};
-  int plan_n[kPlans] = {}, plan_blocks[kPlans] = {};
-  double plan_staged[kPlans] = {};      // touched row pixels staged per node chunk (host model)
-  std::vector<int4> plan_blk[kPlans];  // per block: {ray-range index, group, segment, G}
-  std::vector<char> plan_caseA[kPlans];  // per group: its angles read the transposed image
+  // the group plans (fwd_plan.hpp build_fwd_plans), one of them active: chosen at bind time
+  static constexpr int kPlans = kFwdPlans;
+  FwdPlan plans[kPlans];
+  Buf plan_groups_b[kPlans], plan_rng_b[kPlans];  // their group and ray-range tables on the device
+  const FgGroup* plan_groups(int pl) const { return plan_groups_b[pl].as<const FgGroup>(); }
+  const FgRange* plan_rng(int pl) const { return plan_rng_b[pl].as<const FgRange>(); }
+  int plan_n[kPlans] = {}, plan_blocks[kPlans] = {};  // groups and blocks per node chunk of each plan
+  double plan_staged[kPlans] = {};  // touched row pixels staged per node chunk (host model)
+  const FgGroup* groups = nullptr;  // angle groups of the grouped forward projector (active plan)
+  const FgRange* rng = nullptr;     // its per-block ray ranges
+  int n_groups = 0;                 // 0: geometry does not fit the grouped kernel -> k_fwd
   bool mirror_half = false;  // the half geometry of a mirror-mode context (XCD mapping below)
   Buf fg_order;                       // int4 block table of the grouped forward projector
   int fg_nblk = 0, fg_order_nch = 0;
   int fg_cpb = 1;  // (mirror half geometry) virtual chunks per forward block of the bound table
-  hipStream_t cap = nullptr;  // private capture stream
+  Stream cap;  // private capture stream
 
   // explicit-matrix context (admm_ctx_create_matrix): A and A^T as device CSR, values in
   // the sample dtype; the projector launches dispatch to k_csr_fwd / k_back<..., CSR>
@@ -153,7 +236,7 @@ struct admm_ctx {
   // default), "global" per-pixel global loads; the same results bit for bit
   bool bk_epi_lds = true;
   int n_cu = 0;         // compute units of the device
-  admm_ctx* half = nullptr;
+  std::unique_ptr<admm_ctx> half;
   Buf xs, xsT, p, pT, Hp, sino, bI, fpart, r, c, d2, e2;
   Buf dsumS;  // rho D, D = sum_j q_ij, as interleaved samples (BACK_H epilogue)
   // per-ray weights omega of the bound batch (admm_batch_set_ray_weights), packed into the layout
@@ -165,28 +248,29 @@ struct admm_ctx {
   Buf ats;    // A^T (A xs - b) of the last update's final x (ADMM_BATCH_KEEP_X)
   // admm_time_forward(in_solve): events around every CG-step forward tap launch of one
   // directly enqueued x-update (null outside that measurement)
-  std::vector<hipEvent_t>* tf_ev = nullptr;
+  std::vector<Event>* tf_ev = nullptr;
   size_t tf_next = 0;
   int tf_kind = 0;  // what the in-solve events bracket: 0 forward taps, 1 back projector (BACK_H)
   bool ats_valid = false;  // ats matches x_ext's local rows
-  hipGraph_t g_update_reuse = nullptr;
-  hipGraphExec_t x_update_reuse = nullptr;
   Buf partH, partS, partD, partE;
   Buf redH;
   int P_back = 0, P_tile = 0, P_fwd = 0, P_edge = 0;
-  hipGraph_t g_update = nullptr, g_cons = nullptr;
-  hipGraphExec_t x_update = nullptr, x_cons = nullptr;
+  Graph upd, upd_reuse, cons;  // the recorded x-update, its KEEP_X reuse start, the consensus
+
+  admm_ctx() = default;
+  admm_ctx(const admm_ctx&) = delete;
+  admm_ctx& operator=(const admm_ctx&) = delete;
+  // The context's device is current while everything it holds is released (the half
+  // geometry's context first), then the caller's device comes back: `scope` is the first
+  // member, so it is destroyed after every other one.
+  ~admm_ctx() {
+    scope.enter(device);
+    (void)hipDeviceSynchronize();
+    half.reset();
+  }
 };
 
 namespace {
-
-#define RET(expr)                   \
-  do {                              \
-    int _rc = (expr);               \
-    if (_rc != ADMM_OK) return _rc; \
-  } while (0)
-
-constexpr int kXcds = 8;  // MI355X: 8 XCDs, workgroups dealt round-robin (id % 8)
 
 // Node-interleave width of a batch of V nodes: 32-byte sample vectors at most for float64
 // (8 float64 nodes = 64 B would need 4 sample planes per tap: the forward loses its
@@ -197,73 +281,17 @@ int vb_for(int V, int dtype) {
 }
 
 void select_fwd_plan(admm_ctx* C, int pl) {
-  C->groups = C->plan_groups[pl];
-  C->rng = C->plan_rng[pl];
+  C->groups = C->plan_groups(pl);
+  C->rng = C->plan_rng(pl);
   C->n_groups = C->plan_n[pl];
 }
 
-// Block table of the grouped forward projector for nch node chunks: every live
-// (ray chunk, group, segment, node chunk), sorted by group size G (waves of work), heaviest
-// first.  When every block is resident at once (<= 2 per CU) the second half is reversed so
-// the blocks sharing a CU pair heavy with light (dispatch fills one slot per CU, then the
-// second); otherwise heaviest-first is the longest-processing-time order.
+// Block table of plan pl for nch node chunks in launch order (fwd_plan.hpp fwd_block_order), uploaded
 int build_fwd_order_into(admm_ctx* C, int pl, int nch, int cus, Buf& buf, int* nblk) {
-  struct Blk {
-    int4 b;
-    int w;
-  };
-  std::vector<Blk> v;
-  for (int c = 0; c < nch; ++c)
-    for (const int4& b : C->plan_blk[pl]) v.push_back({make_int4(b.x, b.y, b.z + kFgSeg * c, 0), b.w});
-  const int n = (int)v.size();
-  auto by_weight = [](std::vector<Blk>& l, int slots) {
-    std::stable_sort(l.begin(), l.end(), [](const Blk& a, const Blk& b) { return a.w > b.w; });
-    const int m = (int)l.size();
-    if (m <= 2 * slots && m > slots) std::reverse(l.begin() + slots, l.end());
-  };
-  if (cus > 0 && cus % kXcds == 0) {
-    // XCD-aware: workgroups are dealt round-robin over the 8 XCDs (id % 8), so launch
-    // position p runs on XCD p % 8.  Row segment s goes to XCD s % 8: each XCD's L2 then
-    // holds one band of image rows (and of the transposed copy) instead of re-fetching the
-    // whole image from the Infinity Cache (LDS-DMA staging reads ~10x the image per launch).
-    // Per XCD: heaviest first, the second round reversed (heavy + light per CU pair).
-    // Mirror mode (the half geometry): a case-B block of segment s stages rows of band s
-    // (virtual plane 0) and of band kFgSeg-1-s (plane 1, row N-1-m), a case-A block only
-    // band s of the transposed image (plane 1 mirrors the column).  Segments s and
-    // kFgSeg-1-s therefore share an XCD pair: one XCD takes their case-B blocks, the other
-    // their case-A blocks, so each band of either image lives in one L2 (segment-per-XCD put
-    // every img band in two L2s: FETCH_SIZE 2x, profiles/r4_mirror_xcd.txt).
-    const char* mx = getenv("ADMM_FWD_MIRROR_XCD");  // "0": segment-per-XCD (A/B)
-    const bool paired = C->mirror_half && !(mx && mx[0] == '0');
-    auto xcd_of = [&](const int4& b) {
-      const int sg = b.z % kFgSeg;
-      if (!paired) return sg % kXcds;
-      const int pair = std::min(sg, kFgSeg - 1 - sg);
-      return (2 * pair + (C->plan_caseA[pl][b.y] ? 1 : 0)) % kXcds;
-    };
-    std::vector<std::vector<Blk>> L(kXcds);
-    for (const Blk& b : v) L[xcd_of(b.b)].push_back(b);
-    for (auto& l : L) by_weight(l, cus / kXcds);
-    std::vector<size_t> pos(kXcds, 0);
-    v.clear();
-    for (int p = 0; p < n; ++p) {
-      int x = p % kXcds;
-      if (pos[x] >= L[x].size()) {  // this XCD's segment is used up: the fullest list lends
-        size_t best = 0;
-        for (int y = 0; y < kXcds; ++y)
-          if (L[y].size() - pos[y] > best) best = L[y].size() - pos[y], x = y;
-      }
-      v.push_back(L[x][pos[x]++]);
-    }
-  } else if (cus > 0) {  // cus <= 0: launch order = table order (tuning comparison)
-    by_weight(v, cus);
-  }
-  std::vector<int4> t(n);
-  for (int i = 0; i < n; ++i) t[i] = v[i].b;
-  const int rc = ensure(buf, (size_t)n * sizeof(int4));
-  if (rc != ADMM_OK) return rc;
-  HIPCHK(hipMemcpy(buf.p, t.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice));
-  *nblk = n;
+  const char* mx = getenv("ADMM_FWD_MIRROR_XCD");  // "0": segment-per-XCD (A/B)
+  const std::vector<FgBlock> t = fwd_block_order(C->plans[pl], nch, cus, C->mirror_half, !(mx && mx[0] == '0'));
+  RET(upload(buf, t));
+  *nblk = (int)t.size();
   return ADMM_OK;
 }
 
@@ -273,15 +301,8 @@ int build_fwd_order(admm_ctx* C, int pl, int nch, int cus) {
   return ADMM_OK;
 }
 
-// Forward plan for the bound batch, by rounds of resident blocks: a launch of B blocks on
-// S = (blocks per CU) x CUs slots runs ceil(B / S) rounds, and a partial last round costs
-// nearly a full one (C3 mirror mode: 1024 / 992 blocks = 2 rounds, 65 us; 1056-1296 = 3
-// rounds, 74-84 us; profiles/r4_fwd_plan_rounds.txt).  Among the plans with the fewest
-// rounds, the one staging the fewest row pixels (1024^2, 2048^2: the chunk-aligned plan with
-// clipped rays, 107 / 870 us against 130 / 1020 for the best unclipped one) -- except in a
-// single round, where the 64-ray plan's equal segment shares keep every XCD on its own row
-// band (512^2, one chunk: 33 us against 35-37 for the clipped plans).
-// ADMM_FWD_PLAN=0..5 forces a plan.
+// Forward plan for the bound batch (fwd_plan.hpp choose_fwd_plan_index) on this device's
+// resident slots.  ADMM_FWD_PLAN=0..5 forces a plan.
 // MIRROR / VBR: the instantiation launch_fwdg_taps launches (mirror mode: k_fwdg<T, VBV, true,
 // VBR>, whose piece state and second window buffer set its own registers and LDS), so the
 // occupancy query prices the kernel that actually runs.
@@ -292,16 +313,9 @@ int pick_fwd_plan(admm_ctx* C, int nch, int* pl_out, int* cus_out, long* slots_o
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, C->device));
   if (per_cu < 1) return fail(ADMM_E_HIP, "grouped forward projector cannot be resident");
   const long slots = (long)per_cu * std::max(1, cus);
-  auto rounds = [&](int pl) { return ((long)C->plan_blocks[pl] * nch + slots - 1) / slots; };
-  int pl = 0;
-  for (int q = 1; q < admm_ctx::kPlans; ++q) {
-    if (C->plan_n[q] == 0) continue;
-    if (rounds(q) < rounds(pl) || (rounds(q) == rounds(pl) && C->plan_staged[q] < C->plan_staged[pl])) pl = q;
-  }
-  if (rounds(pl) == 1 && rounds(0) == 1) pl = 0;
   const char* f = getenv("ADMM_FWD_PLAN");
-  if (f && f[0] >= '0' && f[0] < '0' + admm_ctx::kPlans && C->plan_n[f[0] - '0'] > 0) pl = f[0] - '0';
-  *pl_out = pl;
+  const int forced = (f && f[0] >= '0' && f[0] < '0' + admm_ctx::kPlans) ? f[0] - '0' : -1;
+  *pl_out = choose_fwd_plan_index(C->plan_blocks, C->plan_n, C->plan_staged, nch, slots, forced);
   *cus_out = cus;
   if (slots_out) *slots_out = slots;
   return ADMM_OK;
@@ -356,6 +370,22 @@ int with_vb(int vb, F&& f) {
   }
 }
 
+// The sample type of a context: f(type_tag<float>) or f(type_tag<double>)
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+template <typename F>
+int with_type(int dtype, F&& f) {
+  if (dtype == ADMM_DTYPE_F32) return f(type_tag<float>{});
+  return f(type_tag<double>{});
+}
+// ... and the node-interleave width with it: f(type_tag<T>, integral_constant<int, VB>)
+template <typename F>
+int with_type_vb(int dtype, int vb, F&& f) {
+  return with_type(dtype, [&](auto tt) { return with_vb(vb, [&](auto vbc) { return f(tt, vbc); }); });
+}
+
 // Virtual node-interleave width of mirror mode for a real width VBR: twice VBR, at most one
 // 32-byte vector (8 float32 / 4 float64 lanes)
 template <typename T, int VBR>
@@ -398,28 +428,20 @@ int bind_fwd_plan(admm_ctx* C, int V) {
     admm_geom hg = C->g;
     hg.n_angles = C->g.n_angles / 2;
     hg.angle_max = C->g.angle_min + 0.5 * (C->g.angle_max - C->g.angle_min);
-    RET(admm_ctx_create(&C->half, &hg, C->dtype, 1, C->device));  // (tables and plans only)
+    admm_ctx* h = nullptr;
+    RET(admm_ctx_create(&h, &hg, C->dtype, 1, C->device));  // (tables and plans only)
+    C->half.reset(h);
     C->half->mirror_half = true;
     if (C->half->n_groups == 0) C->mm = false;  // (cannot happen: half the angles fit as well)
   }
-  if (C->mm) {
-    RET(with_vb(C->vb, [&](auto vbc) -> int {
-      constexpr int VBR = decltype(vbc)::value;
-      const int nchv = ((V + VBR - 1) / VBR) * (2 * VBR / (C->dtype == ADMM_DTYPE_F32 ? mirror_vb<float, VBR>()
-                                                                                      : mirror_vb<double, VBR>()));
-      if (C->dtype == ADMM_DTYPE_F32) {
-        constexpr int VBV = mirror_vb<float, VBR>();
-        return choose_fwd_plan<float, VBV, true, VBR>(C->half, nchv * VBV);
-      }
-      constexpr int VBV = mirror_vb<double, VBR>();
-      return choose_fwd_plan<double, VBV, true, VBR>(C->half, nchv * VBV);
-    }));
-  } else {
-    RET(with_vb(C->vb, [&](auto vbc) {
-      constexpr int VB = decltype(vbc)::value;
-      return C->dtype == ADMM_DTYPE_F32 ? choose_fwd_plan<float, VB>(C, V) : choose_fwd_plan<double, VB>(C, V);
-    }));
-  }
+  RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) -> int {
+    using T = typename decltype(tt)::type;
+    constexpr int VB = decltype(vbc)::value;
+    if (!C->mm) return choose_fwd_plan<T, VB>(C, V);
+    constexpr int VBV = mirror_vb<T, VB>();
+    const int nchv = ((V + VB - 1) / VB) * (2 * VB / VBV);
+    return choose_fwd_plan<T, VBV, true, VB>(C->half.get(), nchv * VBV);
+  }));
   if (C->n_groups > 0) {
     // (mirror: virtual chunks x half the rays x the virtual width -- the same element count)
     const size_t Vp = (size_t)((V + C->vb - 1) / C->vb) * C->vb;
@@ -443,10 +465,10 @@ int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, do
   }
   dim3 grid((C->g.n_det + kFwdRays - 1) / kFwdRays, C->g.n_angles, (V + VB - 1) / VB);
   if (wts)
-    hipLaunchKernelGGL((k_fwd<T, VB, MODE, const T*>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang,
+    hipLaunchKernelGGL((k_fwd<T, VB, MODE, const T*>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang(),
                        C->g.N, C->g.n_det, C->g.n_angles, V, wts);
   else
-    hipLaunchKernelGGL((k_fwd<T, VB, MODE>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang, C->g.N,
+    hipLaunchKernelGGL((k_fwd<T, VB, MODE>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang(), C->g.N,
                        C->g.n_det, C->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
@@ -457,7 +479,7 @@ int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, do
 template <typename T, int VB>
 int launch_fwdg_taps_with(admm_ctx* C, const T* img, const T* imgT, T* fpart, const FgGroup* groups,
                           const FgRange* rng, const int4* order, int nblk, int V, hipStream_t s) {
-  hipLaunchKernelGGL((k_fwdg<T, VB>), dim3(nblk), dim3(kFgThreads), 0, s, img, imgT, fpart, C->fang, groups, rng,
+  hipLaunchKernelGGL((k_fwdg<T, VB>), dim3(nblk), dim3(kFgThreads), 0, s, img, imgT, fpart, C->fang(), groups, rng,
                      order, C->g.N, C->g.n_det, C->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
@@ -468,19 +490,19 @@ int launch_fwdg_taps(admm_ctx* C, const T* img, const T* imgT, int V, hipStream_
   if (C->mm) {  // mirror mode: virtual chunks of the half geometry (k_fwdg MIRROR)
     constexpr int VBV = mirror_vb<T, VB>(), MH = VBV / 2;
     const int nchv = ((V + VB - 1) / VB) * (VB / MH);
-    const admm_ctx* H = C->half;
+    const admm_ctx* H = C->half.get();
     if (nchv != H->fg_order_nch) return fail(ADMM_E_STATE, "mirror block table built for another batch size");
     if constexpr (fwd_cpb2_ok<T, VBV, true, VB>()) {
       if (H->fg_cpb == 2) {  // two virtual chunks per block (the table holds chunk pairs)
         hipLaunchKernelGGL((k_fwdg<T, VBV, true, VB, 2>), dim3(H->fg_nblk), dim3(kFgThreads), 0, s, img, imgT,
-                           (T*)C->fpart.p, H->fang, H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N,
+                           (T*)C->fpart.p, H->fang(), H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N,
                            C->g.n_det, H->g.n_angles, nchv * VBV);
         CHECK_LAUNCH();
         return ADMM_OK;
       }
     }
     hipLaunchKernelGGL((k_fwdg<T, VBV, true, VB>), dim3(H->fg_nblk), dim3(kFgThreads), 0, s, img, imgT,
-                       (T*)C->fpart.p, H->fang, H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N, C->g.n_det,
+                       (T*)C->fpart.p, H->fang(), H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N, C->g.n_det,
                        H->g.n_angles, nchv * VBV);
     CHECK_LAUNCH();
     return ADMM_OK;
@@ -495,21 +517,21 @@ template <typename T, int VB, int MODE>
 int launch_fwd_batch(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, double* part, int V,
                      hipStream_t s, bool timed = false) {
   // timed (admm_time_forward in_solve): HIP events right before and after the tap kernel
-  hipEvent_t* ev = nullptr;
+  Event* ev = nullptr;
   if (timed && C->tf_ev && C->tf_kind == 0 && C->tf_next + 2 <= C->tf_ev->size()) {
     ev = C->tf_ev->data() + C->tf_next;
     C->tf_next += 2;
-    HIPCHK(hipEventRecord(ev[0], s));
+    HIPCHK(hipEventRecord(ev[0].e, s));
   }
   const T* wts = C->weighted ? (const T*)C->wS.p : nullptr;
   if (C->n_groups == 0) {
     RET((launch_fwd<T, VB, MODE>(C, img, imgT, sino, b, part, V, s, wts)));
-    if (ev) HIPCHK(hipEventRecord(ev[1], s));
+    if (ev) HIPCHK(hipEventRecord(ev[1].e, s));
     return ADMM_OK;
   }
   const int nch = (V + VB - 1) / VB;
   RET((launch_fwdg_taps<T, VB>(C, img, imgT, V, s)));
-  if (ev) HIPCHK(hipEventRecord(ev[1], s));
+  if (ev) HIPCHK(hipEventRecord(ev[1].e, s));
   if (C->mm) {  // virtual partials -> the real sinogram (both angles of every virtual ray)
     constexpr int VBV = mirror_vb<T, VB>(), MH = VBV / 2;
     const int mh = C->half->mrays;
@@ -518,22 +540,37 @@ int launch_fwd_batch(admm_ctx* C, const T* img, const T* imgT, T* sino, const T*
     dim3 mg((unsigned)((mthreads + kBlock - 1) / kBlock), nch * (VB / MH));
     if (wts)
       hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE, const T*>), mg, dim3(kBlock), 0, s,
-                         (const T*)C->fpart.p, sino, b, part, C->half->fang, C->g.n_det, C->half->g.n_angles, V, wts);
+                         (const T*)C->fpart.p, sino, b, part, C->half->fang(), C->g.n_det, C->half->g.n_angles, V, wts);
     else
       hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE>), mg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino,
-                         b, part, C->half->fang, C->g.n_det, C->half->g.n_angles, V);
+                         b, part, C->half->fang(), C->g.n_det, C->half->g.n_angles, V);
     CHECK_LAUNCH();
     return ADMM_OK;
   }
   dim3 cg((C->mrays + kBlock - 1) / kBlock, nch);
   if (wts)
     hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE, const T*>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
-                       C->fang, C->g.n_det, C->g.n_angles, V, wts);
+                       C->fang(), C->g.n_det, C->g.n_angles, V, wts);
   else
     hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
-                       C->fang, C->g.n_det, C->g.n_angles, V);
+                       C->fang(), C->g.n_det, C->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
+}
+
+// The back projectors' geometry arguments: the image and detector of C, the angles of A (C
+// itself, or in mirror mode its half geometry)
+template <typename T>
+void back_geom(BackArgs<T>& a, const admm_ctx* C, const admm_ctx* A, int V) {
+  a.ang = A->bang();
+  a.angc = A->bangc();
+  a.K = A->Kb;
+  a.kbias = A->kbias;
+  a.wexp = A->wexp;
+  a.N = C->g.N;
+  a.n_det = C->g.n_det;
+  a.n_ang = A->g.n_angles;
+  a.V = V;
 }
 
 template <typename T, int VB, int MODE>
@@ -541,16 +578,7 @@ int launch_back(admm_ctx* C, BackArgs<T> a, int V, hipStream_t s) {
   if constexpr (MODE == BACK_H || MODE == BACK_INIT || MODE == BACK_DIAG || MODE == BACK_ATB) {
     if (C->mm) {  // mirror mode: pixel pairs of the upper half, the half geometry's angles
       constexpr int VBV = mirror_vb<T, VB>(), MH = VBV / 2;
-      const admm_ctx* H = C->half;
-      a.ang = H->bang;
-      a.angc = H->bangc;
-      a.K = H->Kb;
-      a.kbias = H->kbias;
-      a.wexp = H->wexp;
-      a.N = C->g.N;
-      a.n_det = C->g.n_det;
-      a.n_ang = H->g.n_angles;
-      a.V = V;
+      back_geom(a, C, C->half.get(), V);
       const int N = C->g.N, Nh = (N + 1) / 2;
       dim3 grid((N + kBTJ - 1) / kBTJ, (Nh + kBTI - 1) / kBTI, ((V + VB - 1) / VB) * (VB / MH));
       void (*kern)(BackArgs<T>) = k_back_mirror<T, VBV, VB, MODE>;
@@ -574,15 +602,7 @@ int launch_back(admm_ctx* C, BackArgs<T> a, int V, hipStream_t s) {
       return ADMM_OK;
     }
   }
-  a.ang = C->bang;
-  a.angc = C->bangc;
-  a.K = C->Kb;
-  a.kbias = C->kbias;
-  a.wexp = C->wexp;
-  a.N = C->g.N;
-  a.n_det = C->g.n_det;
-  a.n_ang = C->g.n_angles;
-  a.V = V;
+  back_geom(a, C, C, V);
   const int N = C->g.N;
   constexpr bool kOneImage = MODE == BACK_WSQ || MODE == BACK_WSQW;  // the column norms: no node chunks
   dim3 grid((N + kBTJ - 1) / kBTJ, (N + kBTI - 1) / kBTI, kOneImage ? 1 : (V + VB - 1) / VB);
@@ -722,14 +742,14 @@ int enqueue_update(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 
       a.lam = B.lam;
       a.mu = B.mu;
       // (admm_time_back: events right before and after each in-solve back projection)
-      hipEvent_t* bev = nullptr;
+      Event* bev = nullptr;
       if (C->tf_ev && C->tf_kind == 1 && C->tf_next + 2 <= C->tf_ev->size()) {
         bev = C->tf_ev->data() + C->tf_next;
         C->tf_next += 2;
-        HIPCHK(hipEventRecord(bev[0], s));
+        HIPCHK(hipEventRecord(bev[0].e, s));
       }
       RET((launch_back<T, VB, BACK_H>(C, a, V, s)));
-      if (bev) HIPCHK(hipEventRecord(bev[1], s));
+      if (bev) HIPCHK(hipEventRecord(bev[1].e, s));
       RET(launch_reduce((double*)C->partH.p, 5 * V, Pb, rk, 1, 1, 0, s));
       if (kk + 1 < K) {
         if (F == 2)
@@ -812,9 +832,10 @@ int enqueue_update(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 
   return ADMM_OK;
 }
 
-template <typename T>
 int enqueue_update_any(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 0) {
-  return with_vb(C->vb, [&](auto vbc) { return enqueue_update<T, decltype(vbc)::value>(C, s, reuse, rounds); });
+  return with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    return enqueue_update<typename decltype(tt)::type, decltype(vbc)::value>(C, s, reuse, rounds);
+  });
 }
 
 // rows of the derived consensus' LDS tile (0: more x_ext rows than any tile: direct kernel)
@@ -880,56 +901,40 @@ int enqueue_consensus(admm_ctx* C, hipStream_t s) {
   return ADMM_OK;
 }
 
-int free_graphs(admm_ctx* C) {
-  if (C->x_update) HIPCHK(hipGraphExecDestroy(C->x_update));
-  if (C->g_update) HIPCHK(hipGraphDestroy(C->g_update));
-  if (C->x_cons) HIPCHK(hipGraphExecDestroy(C->x_cons));
-  if (C->g_cons) HIPCHK(hipGraphDestroy(C->g_cons));
-  C->x_update = nullptr;
-  C->g_update = nullptr;
-  if (C->x_update_reuse) HIPCHK(hipGraphExecDestroy(C->x_update_reuse));
-  if (C->g_update_reuse) HIPCHK(hipGraphDestroy(C->g_update_reuse));
-  C->x_update_reuse = nullptr;
-  C->g_update_reuse = nullptr;
-  C->x_cons = nullptr;
-  C->g_cons = nullptr;
-  return ADMM_OK;
+void free_graphs(admm_ctx* C) {
+  C->upd.reset();
+  C->cons.reset();
+  C->upd_reuse.reset();
 }
 
 template <typename F>
-int capture(admm_ctx* C, F&& fn, hipGraph_t* g, hipGraphExec_t* x) {
-  HIPCHK(hipStreamBeginCapture(C->cap, hipStreamCaptureModeThreadLocal));
-  int rc = fn(C->cap);
-  hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(C->cap, &graph);
+int capture(admm_ctx* C, F&& fn, Graph& out) {
+  HIPCHK(hipStreamBeginCapture(C->cap.s, hipStreamCaptureModeThreadLocal));
+  int rc = fn(C->cap.s);
+  out.reset();
+  hipError_t e = hipStreamEndCapture(C->cap.s, &out.g);
   if (rc != ADMM_OK) {
-    if (graph) (void)hipGraphDestroy(graph);
+    out.reset();
     return rc;
   }
   if (e != hipSuccess) return fail(ADMM_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  HIPCHK(hipGraphInstantiate(x, graph, nullptr, nullptr, 0));
-  *g = graph;
+  HIPCHK(hipGraphInstantiate(&out.x, out.g, nullptr, nullptr, 0));
   return ADMM_OK;
 }
 
 // the bound batch's x-update and consensus sequences, recorded once and replayed every iteration
 // (admm_batch_bind; again by admm_batch_set_ray_weights, whose launches differ)
 int record_graphs(admm_ctx* C) {
-  RET(free_graphs(C));
-  auto fu = [&](hipStream_t s) {
-    return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s) : enqueue_update_any<double>(C, s);
-  };
-  RET(capture(C, fu, &C->g_update, &C->x_update));
+  free_graphs(C);
+  auto fu = [&](hipStream_t s) { return enqueue_update_any(C, s); };
+  RET(capture(C, fu, C->upd));
   if (C->b.flags & ADMM_BATCH_KEEP_X) {
-    auto fr = [&](hipStream_t s) {
-      return C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s, true)
-                                        : enqueue_update_any<double>(C, s, true);
-    };
-    RET(capture(C, fr, &C->g_update_reuse, &C->x_update_reuse));
+    auto fr = [&](hipStream_t s) { return enqueue_update_any(C, s, true); };
+    RET(capture(C, fr, C->upd_reuse));
   }
   if (C->b.n_edges > 0) {
     auto fc = [&](hipStream_t s) { return enqueue_consensus(C, s); };
-    RET(capture(C, fc, &C->g_cons, &C->x_cons));
+    RET(capture(C, fc, C->cons));
   }
   return ADMM_OK;
 }
@@ -956,10 +961,10 @@ int op_forward_chunk(admm_ctx* C, const T* img, T* sino, int nc, hipStream_t s) 
   CHECK_LAUNCH();
   hipLaunchKernelGGL((k_transpose<T, VB>), tile_grid(C, 1, VB), dim3(kBlock), 0, s, (const T*)xs, xsT, C->g.N);
   CHECK_LAUNCH();
-  RET((launch_fwdg_taps_with<T, VB>(C, xs, xsT, (T*)C->op_fpart.p, C->plan_groups[pl], C->plan_rng[pl],
+  RET((launch_fwdg_taps_with<T, VB>(C, xs, xsT, (T*)C->op_fpart.p, C->plan_groups(pl), C->plan_rng(pl),
                                     (const int4*)C->op_order[pl].p, C->op_nblk[pl], nc, s)));
   hipLaunchKernelGGL((k_fwd_combine<T, VB, 0>), dim3((m + kBlock - 1) / kBlock, 1), dim3(kBlock), 0, s,
-                     (const T*)C->op_fpart.p, sI, (const T*)nullptr, (double*)nullptr, C->fang, C->g.n_det,
+                     (const T*)C->op_fpart.p, sI, (const T*)nullptr, (double*)nullptr, C->fang(), C->g.n_det,
                      C->g.n_angles, nc);
   CHECK_LAUNCH();
   hipLaunchKernelGGL((k_unpack<T, VB>), dim3((m + 255) / 256, 1), dim3(256), 0, s, (const T*)sI, sino, m, nc);
@@ -1008,21 +1013,13 @@ int admm_ctx_create(admm_ctx** out, const admm_geom* geom, int dtype, int max_im
   if (!out || !geom) return fail(ADMM_E_INVALID, "null argument");
   *out = nullptr;
   const admm_geom g = *geom;
-  if (g.N < 2 || g.n_angles < 1 || g.n_det < 1) return fail(ADMM_E_INVALID, "bad geometry sizes");
-  if (g.N > 4096) return fail(ADMM_E_INVALID, "N > 4096 is not supported");
-  if (dtype != ADMM_DTYPE_F32 && dtype != ADMM_DTYPE_F64) return fail(ADMM_E_INVALID, "bad dtype");
-  if (max_images < 1) return fail(ADMM_E_INVALID, "max_images < 1");
-  const double h = 2.0 / g.N;
-  const double hd = (g.det_max - g.det_min) / g.n_det;
-  if (!(hd > 0)) return fail(ADMM_E_INVALID, "det_max <= det_min");
-  if (hd < h * (1.0 - 1e-9))
-    return fail(ADMM_E_INVALID, "detector spacing finer than the pixel size is not supported "
-                                "(det_width_factor must be >= 1 with n_det = N)");
-  const size_t npix = (size_t)g.N * g.N, m = (size_t)g.n_angles * g.n_det;
-  if ((size_t)max_images * npix * 8 >= (1ull << 31) || (size_t)max_images * m * 8 >= (1ull << 31))
-    return fail(ADMM_E_INVALID, "batch too large for 32-bit buffer offsets; split it across contexts");
+  // validate -> geometry tables -> forward plans (fwd_plan.hpp, host only) -> upload
+  if (const char* err = check_geom(g, dtype, max_images)) return fail(ADMM_E_INVALID, err);
+  GeomTables T;
+  if (const char* err = geom_tables(g, dtype, T)) return fail(ADMM_E_INVALID, err);
+  FwdPlans P = build_fwd_plans(g, T.fa);
   DEVICE_SCOPE(device);
-  admm_ctx* C = new admm_ctx();
+  std::unique_ptr<admm_ctx> C(new admm_ctx());
   C->g = g;
   C->dtype = dtype;
   C->device = device;
@@ -1035,257 +1032,29 @@ int admm_ctx_create(admm_ctx** out, const admm_geom* geom, int dtype, int max_im
   }
   HIPCHK(hipDeviceGetAttribute(&C->n_cu, hipDeviceAttributeMultiprocessorCount, device));
   C->max_images = max_images;
-  C->npix = (int)npix;
-  C->mrays = (int)m;
-
-  // geometry tables, float64 (oracle/geometry.py)
-  std::vector<FwdAngle> fa(g.n_angles);
-  std::vector<BackAngle> ba(g.n_angles);
-  std::vector<BackAngleC> bc(g.n_angles);
-  C->Kb = -g.det_min / hd - 0.5;
-  const double c0 = 0.5 * (g.N - 1);
-  for (int t = 0; t < g.n_angles; ++t) {
-    const double th = g.angle_min + (t + 0.5) * (g.angle_max - g.angle_min) / g.n_angles;
-    const double cs = std::cos(th), sn = std::sin(th);
-    const bool caseA = std::fabs(cs) >= std::fabs(sn);
-    const double al = caseA ? cs : sn, be = caseA ? sn : cs;
-    fa[t].A0 = c0 + (g.det_min / h + 0.5 * hd / h + c0 * be) / al;
-    fa[t].A1 = (hd / h) / al;
-    fa[t].dl = -be / al;
-    fa[t].L = h / std::fabs(al);
-    fa[t].caseA = caseA ? 1 : 0;
-    ba[t].Bi = cs * h / hd;
-    ba[t].Bj = sn * h / hd;
-    ba[t].B0 = -c0 * (ba[t].Bi + ba[t].Bj) - g.det_min / hd - 0.5;
-    ba[t].slope = (hd / h) / std::fabs(al);
-    ba[t].L = h / std::fabs(al);
-    bc[t].Bi = ba[t].Bi;
-    bc[t].Bj = ba[t].Bj;
-    const float sLf = (float)(ba[t].slope * ba[t].L);
-    bc[t].ws = float2v{-sLf, sLf};
-    bc[t].wc = float2v{(float)ba[t].L, (float)(ba[t].L - ba[t].slope * ba[t].L)};
-    while (std::ldexp((double)bc[t].wc.x, -C->wexp) > 1.0) ++C->wexp;
-    // smallest k_f of any pixel at this angle: Kb - c0 (|Bi| + |Bj|)
-    const double kmn = C->Kb - c0 * (std::fabs(ba[t].Bi) + std::fabs(ba[t].Bj));
-    C->kbias = std::max(C->kbias, (int)std::ceil(-kmn) + 2);
-  }
-  // the float taps' kf_split needs k_f + kbias in (0, 2^20) for every pixel and angle (the sum
-  // with 2^20 must stay in [2^20, 2^21)); a detector far off the image could break that
-  for (int t = 0; t < g.n_angles && dtype == ADMM_DTYPE_F32; ++t) {
-    const double kmx = C->Kb + C->kbias + c0 * (std::fabs(ba[t].Bi) + std::fabs(ba[t].Bj)) + 2.0;
-    if (kmx >= 1048576.0) {
-      delete C;  // (nothing allocated on the device yet)
-      return fail(ADMM_E_INVALID, "detector offset puts a bin position past 2^20 (kf_split)");
+  C->npix = g.N * g.N;
+  C->mrays = g.n_angles * g.n_det;
+  C->Kb = T.Kb;
+  C->kbias = T.kbias;
+  C->wexp = T.wexp;
+  RET(upload(C->fang_b, T.fa));
+  RET(upload(C->bang_b, T.ba));
+  RET(upload(C->bangc_b, T.bc));
+  if (P.fits) {
+    for (int pl = 0; pl < admm_ctx::kPlans; ++pl) {
+      FwdPlan& Q = P.plan[pl];
+      if (Q.groups.empty()) continue;
+      RET(upload(C->plan_groups_b[pl], Q.groups));
+      RET(upload(C->plan_rng_b[pl], Q.ranges));
+      C->plan_n[pl] = (int)Q.groups.size();
+      C->plan_blocks[pl] = (int)Q.blocks.size();
+      C->plan_staged[pl] = Q.staged;
+      C->plans[pl] = std::move(Q);
     }
+    select_fwd_plan(C.get(), 0);  // until a batch is bound
   }
-  // exact power-of-two scalings: 2^-wexp (N < 3: L = 2 / (N |cos|) can exceed 1) on ws and wc, and
-  // 2^-32 on ws, whose float taps multiply frac(k_f) x 2^32 (kernels.hpp kf_split)
-  for (int t = 0; t < g.n_angles; ++t) {
-    bc[t].ws = float2v{std::ldexp(bc[t].ws.x, -C->wexp - 32), std::ldexp(bc[t].ws.y, -C->wexp - 32)};
-    bc[t].wc = float2v{std::ldexp(bc[t].wc.x, -C->wexp), std::ldexp(bc[t].wc.y, -C->wexp)};
-  }
-  // angle groups for the grouped forward projector: consecutive angles of one case,
-  // G <= kFgG, whose union row window of every block fits kFgWin (float64, same formulas as
-  // the device; 2 pixels of margin).  Three plans, each a table of per-block ray ranges
-  // (FgRange): plain 64-ray chunks; 64-ray chunks aligned per (row segment, angle) at the
-  // detector centre (FgGroup.delta: narrower windows and larger groups, one more chunk per
-  // segment); chunks aligned per (row segment, chunk) -- every angle's chunk x starts at the
-  // same pixel of the segment's centre row, so windows stay narrow far from the detector
-  // centre, where the rays' spacing 1/|cos| differs between the group's angles.
-  // admm_batch_bind picks one (pick_fwd_plan).
-  constexpr int kPlans = admm_ctx::kPlans;
-  std::vector<FgGroup> groups_plan[kPlans];
-  std::vector<FgRange> rng_plan[kPlans];
-  std::vector<int4> blk_plan[kPlans];
-  double staged_plan[kPlans] = {};
-  bool fits = true;
-  {
-    const double cd = 0.5 * (g.n_det - 1);
-    // touched row pixels of one block over its segment's rows, -1 if a row is too wide
-    auto window_px = [&](int t0, int G, int mlo, int mhi, const FgRange& r) -> long {
-      long px = 0;
-      for (int m = mlo; m < mhi; ++m) {
-        double lo = 1e300, hi = -1e300;
-        for (int q = 0; q < G; ++q) {
-          if (r.nk[q] == 0) continue;
-          const FwdAngle& b = fa[t0 + q];
-          for (int kk : {r.k0[q], r.k0[q] + r.nk[q] - 1}) {
-            const double l = std::fma((double)m, b.dl, std::fma((double)kk, b.A1, b.A0));
-            lo = std::min(lo, l);
-            hi = std::max(hi, l);
-          }
-        }
-        if (lo > hi) continue;
-        const double w = std::floor(hi) - std::floor(lo) + 2;
-        if (w > kFgWin - 2) return -1;
-        px += (long)w;
-      }
-      return px;
-    };
-    // the blocks of group (t0, G) under plan pl: ray ranges rv, block entries bv
-    // ({range index within rv, group index gi, segment, G}), staged pixels st
-    auto plan_group = [&](int t0, int G, int pl, int gi, FgGroup& gr, std::vector<FgRange>& rv,
-                          std::vector<int4>& bv, double& st) -> bool {
-      for (int q = 0; q < G; ++q)
-        if (fa[t0 + q].caseA != fa[t0].caseA) return false;
-      const int scheme = pl % 3;
-      const bool clipped = pl >= 3;
-      gr = FgGroup{};
-      gr.t0 = t0;
-      gr.G = G;
-      rv.clear();
-      bv.clear();
-      st = 0.0;
-      for (int s = 0; s < kFgSeg; ++s) {
-        const int mlo = s * g.N / kFgSeg, mhi = (s + 1) * g.N / kFgSeg;
-        const double mc = 0.5 * (mlo + mhi - 1);
-        // only rays that cross the segment's rows inside the image get lanes: a ray whose every
-        // row position l lies outside [-2, N + 1] taps zero-filled columns only, so its partial
-        // for this segment is exactly 0 and its slot keeps the zero it was filled with
-        // (admm_batch_bind / op_forward_chunk zero the partials when the plan changes)
-        const double dlo = std::min(mlo * 1.0, mhi - 1.0), dhi = std::max(mlo * 1.0, mhi - 1.0);
-        auto clip = [&](FgRange& r) {
-          for (int q = 0; q < G; ++q) {
-            const FwdAngle& b = fa[t0 + q];
-            const double e0 = std::min(dlo * b.dl, dhi * b.dl), e1 = std::max(dlo * b.dl, dhi * b.dl);
-            const double ka = (-2.0 - b.A0 - e1) / b.A1, kb = (g.N + 1.0 - b.A0 - e0) / b.A1;
-            const double klo = std::ceil(std::min(ka, kb)), khi = std::floor(std::max(ka, kb));
-            const int lo = (int)std::max((double)r.k0[q], klo);
-            const int hi = (int)std::min((double)(r.k0[q] + r.nk[q]), khi + 1.0);
-            r.nk[q] = std::max(0, hi - lo);
-            r.k0[q] = std::min(std::max(lo, 0), g.n_det - 1);
-          }
-        };
-        auto emit = [&](FgRange r) -> bool {
-          if (clipped) clip(r);
-          bool any = false;
-          for (int q = 0; q < G; ++q) any = any || r.nk[q] > 0;
-          if (!any) return true;
-          const long px = window_px(t0, G, mlo, mhi, r);
-          if (px < 0) return false;
-          st += (double)px;
-          bv.push_back(make_int4((int)rv.size(), gi, s, G));
-          rv.push_back(r);
-          return true;
-        };
-        if (scheme < 2) {
-          const FwdAngle& r0 = fa[t0];
-          const double lref = r0.A0 + cd * r0.A1 + mc * r0.dl;  // reference ray at the centre row
-          int delta[kFgG] = {};  // per-angle ray offset of the 64-ray chunks (scheme 1)
-          int dmin = 0, dmax = 0;
-          for (int q = 0; q < G; ++q) {
-            const FwdAngle& b = fa[t0 + q];
-            const int d = scheme == 1 ? (int)std::lround((lref - b.A0 - cd * b.A1 - mc * b.dl) / b.A1) : 0;
-            delta[q] = d;
-            dmin = std::min(dmin, d);
-            dmax = std::max(dmax, d);
-          }
-          const int kcb = (int)std::floor(-dmax / 64.0);
-          const int kce = (int)std::ceil((g.n_det - dmin) / 64.0);
-          for (int kc = kcb; kc < kce; ++kc) {
-            FgRange r{};
-            for (int q = 0; q < G; ++q) {
-              const int lo = std::max(kc * 64 + delta[q], 0);
-              const int hi = std::min(kc * 64 + delta[q] + 64, g.n_det);
-              r.k0[q] = lo;
-              r.nk[q] = std::max(0, hi - lo);
-            }
-            if (!emit(r)) return false;
-          }
-        } else {
-          // position of ray k at the centre row, along the direction of increasing k:
-          // u_q(k) = sgn (A0 + mc dl) + k |A1|; chunk x holds the rays with u in
-          // [U0 + x S, U0 + (x + 1) S), S = 64 min|A1| (<= 64 rays of every angle)
-          const double sgn = fa[t0].A1 > 0 ? 1.0 : -1.0;
-          double amin = 1e300, U0 = 1e300;
-          double cq[kFgG], aq[kFgG];
-          for (int q = 0; q < G; ++q) {
-            const FwdAngle& b = fa[t0 + q];
-            if ((b.A1 > 0) != (sgn > 0)) return false;
-            aq[q] = std::fabs(b.A1);
-            cq[q] = sgn * (b.A0 + mc * b.dl);
-            amin = std::min(amin, aq[q]);
-            U0 = std::min(U0, cq[q]);
-          }
-          const double S = 64.0 * amin * (1.0 - 1e-9);
-          auto bnd = [&](int q, long x) {
-            const double v = std::ceil((U0 + (double)x * S - cq[q]) / aq[q]);
-            return (int)std::min(std::max(v, 0.0), (double)g.n_det);
-          };
-          for (long x = 0;; ++x) {
-            if (x > 4L * g.n_det + 8) return false;  // (cannot happen: every chunk spans >= 64 pixels)
-            FgRange r{};
-            bool done = true;
-            for (int q = 0; q < G; ++q) {
-              const int lo = bnd(q, x), hi = bnd(q, x + 1);
-              done = done && lo >= g.n_det;
-              r.k0[q] = std::min(lo, g.n_det - 1);
-              r.nk[q] = hi - lo;
-              if (r.nk[q] > 64) return false;
-            }
-            if (done) break;
-            if (!emit(r)) return false;
-          }
-        }
-      }
-      return true;
-    };
-    // greedy: the largest G <= kFgG consecutive same-case angles whose windows fit.
-    // (Balanced splits of each same-case run were measured slower: they force wide windows
-    // near 45 degrees, where greedy makes small narrow groups and stages fewer pixels.)
-    for (int pl = 0; pl < kPlans && fits; ++pl) {
-      for (int t0 = 0; t0 < g.n_angles;) {
-        int G = std::min(kFgG, g.n_angles - t0);
-        const int gi = (int)groups_plan[pl].size();
-        FgGroup gr{};
-        std::vector<FgRange> rv;
-        std::vector<int4> bv;
-        double st = 0.0;
-        while (G > 1 && !plan_group(t0, G, pl, gi, gr, rv, bv, st)) --G;
-        if (G == 1 && !plan_group(t0, 1, pl, gi, gr, rv, bv, st)) {
-          if (pl < 2) fits = false;  // no grouped kernel for this geometry
-          groups_plan[pl].clear();   // (plans 2-5 are optional)
-          break;
-        }
-        const int base = (int)rng_plan[pl].size();
-        for (int4 b : bv) blk_plan[pl].push_back(make_int4(b.x + base, b.y, b.z, b.w));
-        rng_plan[pl].insert(rng_plan[pl].end(), rv.begin(), rv.end());
-        groups_plan[pl].push_back(gr);
-        staged_plan[pl] += st;
-        t0 += G;
-      }
-    }
-  }
-  hipError_t e1 = hipMalloc(&C->fang, fa.size() * sizeof(FwdAngle));
-  hipError_t e2 = hipMalloc(&C->bang, ba.size() * sizeof(BackAngle));
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    delete C;
-    return fail(ADMM_E_HIP, "hipMalloc geometry tables");
-  }
-  HIPCHK(hipMemcpy(C->fang, fa.data(), fa.size() * sizeof(FwdAngle), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(C->bang, ba.data(), ba.size() * sizeof(BackAngle), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&C->bangc, bc.size() * sizeof(BackAngleC)));
-  HIPCHK(hipMemcpy(C->bangc, bc.data(), bc.size() * sizeof(BackAngleC), hipMemcpyHostToDevice));
-  if (fits) {
-    for (int pl = 0; pl < kPlans; ++pl) {
-      const auto& gv = groups_plan[pl];
-      const auto& rv = rng_plan[pl];
-      if (gv.empty()) continue;
-      HIPCHK(hipMalloc(&C->plan_groups[pl], gv.size() * sizeof(FgGroup)));
-      HIPCHK(hipMemcpy(C->plan_groups[pl], gv.data(), gv.size() * sizeof(FgGroup), hipMemcpyHostToDevice));
-      HIPCHK(hipMalloc(&C->plan_rng[pl], rv.size() * sizeof(FgRange)));
-      HIPCHK(hipMemcpy(C->plan_rng[pl], rv.data(), rv.size() * sizeof(FgRange), hipMemcpyHostToDevice));
-      C->plan_blk[pl] = blk_plan[pl];
-      C->plan_caseA[pl].clear();
-      for (const FgGroup& gr : gv) C->plan_caseA[pl].push_back(fa[gr.t0].caseA != 0);
-      C->plan_n[pl] = (int)gv.size();
-      C->plan_blocks[pl] = (int)blk_plan[pl].size();
-      C->plan_staged[pl] = staged_plan[pl];
-    }
-    select_fwd_plan(C, 0);  // until a batch is bound
-  }
-  HIPCHK(hipStreamCreateWithFlags(&C->cap, hipStreamNonBlocking));
-  *out = C;
+  HIPCHK(hipStreamCreateWithFlags(&C->cap.s, hipStreamNonBlocking));
+  *out = C.release();
   return ADMM_OK;
 }
 
@@ -1322,7 +1091,7 @@ int admm_ctx_create_matrix(admm_ctx** out, int N, int m, long long nnz, const lo
   std::vector<int> fptr(m + 1);
   for (int r = 0; r <= m; ++r) fptr[r] = (int)indptr[r];
   DEVICE_SCOPE(device);
-  admm_ctx* C = new admm_ctx();
+  std::unique_ptr<admm_ctx> C(new admm_ctx());
   // a one-"angle" geometry (n_det = m, L = 1): every m-sized buffer, the fixed-order
   // reductions and the combine/residual kernels keep their shapes
   C->g = admm_geom{};
@@ -1340,65 +1109,27 @@ int admm_ctx_create_matrix(admm_ctx** out, int N, int m, long long nnz, const lo
   fa.L = 1.0;
   BackAngle ba{};
   BackAngleC bc{};
-  int rc = ADMM_OK;
-  auto up = [&](Buf& b, const void* src, size_t bytes) {
-    if (rc != ADMM_OK) return;
-    rc = ensure(b, std::max<size_t>(bytes, 16));
-    if (rc == ADMM_OK && bytes > 0 && hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail(ADMM_E_HIP, "hipMemcpy (matrix upload)");
-  };
+  // the values in the sample dtype
   auto upv = [&](Buf& b, const std::vector<double>& v) {
-    if (dtype == ADMM_DTYPE_F64) return up(b, v.data(), v.size() * 8);
-    std::vector<float> f(v.begin(), v.end());
-    up(b, f.data(), f.size() * 4);
+    if (dtype == ADMM_DTYPE_F64) return upload(b, v, 16);
+    return upload(b, std::vector<float>(v.begin(), v.end()), 16);
   };
-  up(C->f_ptr, fptr.data(), fptr.size() * 4);
-  up(C->f_idx, indices, (size_t)nnz * 4);
-  upv(C->f_val, std::vector<double>(values, values + nnz));
-  up(C->t_ptr, tptr.data(), tptr.size() * 4);
-  up(C->t_idx, tidx.data(), tidx.size() * 4);
-  upv(C->t_val, tval);
-  if (rc == ADMM_OK && (hipMalloc(&C->fang, sizeof(FwdAngle)) != hipSuccess ||
-                        hipMalloc(&C->bang, sizeof(BackAngle)) != hipSuccess ||
-                        hipMalloc(&C->bangc, sizeof(BackAngleC)) != hipSuccess))
-    rc = fail(ADMM_E_HIP, "hipMalloc tables");
-  if (rc == ADMM_OK && (hipMemcpy(C->fang, &fa, sizeof(fa), hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemcpy(C->bang, &ba, sizeof(ba), hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemcpy(C->bangc, &bc, sizeof(bc), hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(ADMM_E_HIP, "hipMemcpy tables");
-  if (rc == ADMM_OK && hipStreamCreateWithFlags(&C->cap, hipStreamNonBlocking) != hipSuccess)
-    rc = fail(ADMM_E_HIP, "hipStreamCreate");
-  if (rc != ADMM_OK) {
-    const std::string msg = g_err;
-    admm_ctx_destroy(C);
-    return fail(rc, msg);
-  }
-  *out = C;
+  RET(upload(C->f_ptr, fptr, 16));
+  RET(upload(C->f_idx, indices, (size_t)nnz * 4, 16));
+  RET(upv(C->f_val, std::vector<double>(values, values + nnz)));
+  RET(upload(C->t_ptr, tptr, 16));
+  RET(upload(C->t_idx, tidx, 16));
+  RET(upv(C->t_val, tval));
+  RET(upload(C->fang_b, &fa, sizeof(fa)));
+  RET(upload(C->bang_b, &ba, sizeof(ba)));
+  RET(upload(C->bangc_b, &bc, sizeof(bc)));
+  HIPCHK(hipStreamCreateWithFlags(&C->cap.s, hipStreamNonBlocking));
+  *out = C.release();
   return ADMM_OK;
 }
 
 int admm_ctx_destroy(admm_ctx* C) {
   if (!C) return ADMM_OK;
-  DeviceGuard _dg(C->device);
-  (void)hipDeviceSynchronize();
-  free_graphs(C);
-  if (C->half) (void)admm_ctx_destroy(C->half);
-  C->half = nullptr;
-  Buf* bufs[] = {&C->op_img, &C->op_imgT, &C->op_sino, &C->op_fpart, &C->xs, &C->xsT, &C->p, &C->pT, &C->Hp, &C->sino, &C->bI, &C->fpart, &C->r, &C->c,
-                 &C->d2, &C->e2, &C->partH, &C->partS, &C->partD, &C->partE, &C->redH, &C->fg_order, &C->dsumS, &C->ats,
-                 &C->f_ptr, &C->f_idx, &C->f_val, &C->t_ptr, &C->t_idx, &C->t_val, &C->x2, &C->p2, &C->pring, &C->wS};
-  for (Buf* b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  for (Buf& b : C->op_order)
-    if (b.p) (void)hipFree(b.p);
-  if (C->fang) (void)hipFree(C->fang);
-  if (C->bang) (void)hipFree(C->bang);
-  if (C->bangc) (void)hipFree(C->bangc);
-  for (FgGroup* pg : C->plan_groups)
-    if (pg) (void)hipFree(pg);
-  for (FgRange* pr : C->plan_rng)
-    if (pr) (void)hipFree(pr);
-  if (C->cap) (void)hipStreamDestroy(C->cap);
   delete C;
   return ADMM_OK;
 }
@@ -1408,8 +1139,10 @@ int admm_project_fwd(admm_ctx* C, const void* img, void* sino, int nimg, void* s
   if (nimg < 1 || nimg > C->max_images) return fail(ADMM_E_INVALID, "nimg out of range");
   hipStream_t s = (hipStream_t)stream;
   DEVICE_SCOPE(C->device);
-  return C->dtype == ADMM_DTYPE_F32 ? op_forward<float>(C, (const float*)img, (float*)sino, nimg, s)
-                                    : op_forward<double>(C, (const double*)img, (double*)sino, nimg, s);
+  return with_type(C->dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    return op_forward<T>(C, (const T*)img, (T*)sino, nimg, s);
+  });
 }
 
 int admm_project_adj(admm_ctx* C, const void* sino, void* img, int nimg, void* stream) {
@@ -1417,30 +1150,25 @@ int admm_project_adj(admm_ctx* C, const void* sino, void* img, int nimg, void* s
   if (nimg < 1 || nimg > C->max_images) return fail(ADMM_E_INVALID, "nimg out of range");
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
-  if (C->dtype == ADMM_DTYPE_F32) {
-    BackArgs<float> a{};
-    a.sino = (const float*)sino;
-    a.out_t = (float*)img;
-    return launch_back<float, 1, BACK_PLAIN>(C, a, nimg, s);
-  }
-  BackArgs<double> a{};
-  a.sino = (const double*)sino;
-  a.out_t = (double*)img;
-  return launch_back<double, 1, BACK_PLAIN>(C, a, nimg, s);
+  return with_type(C->dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    BackArgs<T> a{};
+    a.sino = (const T*)sino;
+    a.out_t = (T*)img;
+    return launch_back<T, 1, BACK_PLAIN>(C, a, nimg, s);
+  });
 }
 
 int admm_column_norms_sq(admm_ctx* C, double* W, void* stream) {
   if (!C || !W) return fail(ADMM_E_INVALID, "null argument");
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
-  if (C->dtype == ADMM_DTYPE_F32) {
-    BackArgs<float> a{};
+  return with_type(C->dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    BackArgs<T> a{};
     a.out_d = W;
-    return launch_back<float, 1, BACK_WSQ>(C, a, 1, s);
-  }
-  BackArgs<double> a{};
-  a.out_d = W;
-  return launch_back<double, 1, BACK_WSQ>(C, a, 1, s);
+    return launch_back<T, 1, BACK_WSQ>(C, a, 1, s);
+  });
 }
 
 int admm_column_norms_sq_weighted(admm_ctx* C, const void* w, double* W, void* stream) {
@@ -1450,16 +1178,13 @@ int admm_column_norms_sq_weighted(admm_ctx* C, const void* w, double* W, void* s
                                 "the rows of A by sqrt(omega) instead (exact there)");
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
-  if (C->dtype == ADMM_DTYPE_F32) {
-    BackArgs<float> a{};
-    a.sino = (const float*)w;
+  return with_type(C->dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    BackArgs<T> a{};
+    a.sino = (const T*)w;
     a.out_d = W;
-    return launch_back<float, 1, BACK_WSQW>(C, a, 1, s);
-  }
-  BackArgs<double> a{};
-  a.sino = (const double*)w;
-  a.out_d = W;
-  return launch_back<double, 1, BACK_WSQW>(C, a, 1, s);
+    return launch_back<T, 1, BACK_WSQW>(C, a, 1, s);
+  });
 }
 
 int admm_tv_grad(admm_ctx* C, const double* x, double* gx, double* gy, int nimg, void* stream) {
@@ -1509,7 +1234,7 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
     return fail(ADMM_E_INVALID, "batch too large for 32-bit buffer offsets");
   DEVICE_SCOPE(C->device);
   HIPCHK(hipDeviceSynchronize());
-  RET(free_graphs(C));
+  free_graphs(C);
   C->b = B;
   C->weighted = false;  // a bind drops the per-ray weights (admm_batch_set_ray_weights)
   const int V = B.V;
@@ -1555,19 +1280,16 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
   // rho D, D = sum_j q_ij, as interleaved samples of the sample dtype (the BACK_H epilogue's
   // rho D p term): setup data, packed and scaled once here rather than in every x-update (rho
   // is the bound batch's; a re-bind packs again)
-  RET(with_vb(C->vb, [&](auto vbc) {
+  RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    using T = typename decltype(tt)::type;
     constexpr int VB = decltype(vbc)::value;
     const int nch = (V + VB - 1) / VB;
-    if (C->dtype == ADMM_DTYPE_F32)
-      hipLaunchKernelGGL((k_pack_d<float, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap,
-                         B.dsum, (float*)C->dsumS.p, (int)npix, V, B.rho);
-    else
-      hipLaunchKernelGGL((k_pack_d<double, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap,
-                         B.dsum, (double*)C->dsumS.p, (int)npix, V, B.rho);
+    hipLaunchKernelGGL((k_pack_d<T, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap.s, B.dsum,
+                       (T*)C->dsumS.p, (int)npix, V, B.rho);
     CHECK_LAUNCH();
     return ADMM_OK;
   }));
-  HIPCHK(hipStreamSynchronize(C->cap));
+  HIPCHK(hipStreamSynchronize(C->cap.s));
   RET(record_graphs(C));
   HIPCHK(hipDeviceSynchronize());
   return ADMM_OK;
@@ -1589,13 +1311,11 @@ int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
     const int V = C->b.V, m = C->mrays;
     const size_t Vp = (size_t)((V + C->vb - 1) / C->vb) * C->vb;
     RET(ensure(C->wS, Vp * m * dsize(C->dtype)));
-    RET(with_vb(C->vb, [&](auto vbc) {
+    RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+      using T = typename decltype(tt)::type;
       constexpr int VB = decltype(vbc)::value;
       const dim3 grid((m + 255) / 256, (V + VB - 1) / VB);
-      if (C->dtype == ADMM_DTYPE_F32)
-        hipLaunchKernelGGL((k_pack<float, VB>), grid, dim3(256), 0, s, (const float*)w, (float*)C->wS.p, m, V);
-      else
-        hipLaunchKernelGGL((k_pack<double, VB>), grid, dim3(256), 0, s, (const double*)w, (double*)C->wS.p, m, V);
+      hipLaunchKernelGGL((k_pack<T, VB>), grid, dim3(256), 0, s, (const T*)w, (T*)C->wS.p, m, V);
       CHECK_LAUNCH();
       return ADMM_OK;
     }));
@@ -1607,11 +1327,14 @@ int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
   return ADMM_OK;
 }
 
-extern "C++" {
-template <typename T>
-int batch_atb(admm_ctx* C, double* atb_out, hipStream_t s) {
+int admm_batch_atb(admm_ctx* C, double* atb_out, void* stream) {
+  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
+  if (!atb_out) return fail(ADMM_E_INVALID, "null atb_out");
+  DEVICE_SCOPE(C->device);
+  hipStream_t s = (hipStream_t)stream;
   const int V = C->b.V;
-  return with_vb(C->vb, [&](auto vbc) {
+  return with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    using T = typename decltype(tt)::type;
     constexpr int VB = decltype(vbc)::value;
     const int nch = (V + VB - 1) / VB;
     if (C->weighted)  // A^T (omega b)
@@ -1627,15 +1350,6 @@ int batch_atb(admm_ctx* C, double* atb_out, hipStream_t s) {
     return launch_back<T, VB, BACK_ATB>(C, a, V, s);
   });
 }
-}  // extern "C++"
-
-int admm_batch_atb(admm_ctx* C, double* atb_out, void* stream) {
-  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
-  if (!atb_out) return fail(ADMM_E_INVALID, "null atb_out");
-  DEVICE_SCOPE(C->device);
-  hipStream_t s = (hipStream_t)stream;
-  return C->dtype == ADMM_DTYPE_F32 ? batch_atb<float>(C, atb_out, s) : batch_atb<double>(C, atb_out, s);
-}
 
 int admm_node_update(admm_ctx* C, void* stream) {
   if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
@@ -1644,11 +1358,10 @@ int admm_node_update(admm_ctx* C, void* stream) {
   const bool keep = (C->b.flags & ADMM_BATCH_KEEP_X) != 0;
   const bool reuse = keep && C->ats_valid;
   int rc = ADMM_OK;
-  if (C->x_update) {
-    HIPCHK(hipGraphLaunch(reuse ? C->x_update_reuse : C->x_update, s));
+  if (C->upd.x) {
+    HIPCHK(hipGraphLaunch(reuse ? C->upd_reuse.x : C->upd.x, s));
   } else {
-    rc = C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s, reuse)
-                                    : enqueue_update_any<double>(C, s, reuse);
+    rc = enqueue_update_any(C, s, reuse);
   }
   if (rc == ADMM_OK && keep) C->ats_valid = true;  // this update's DIAG left A^T s of its x
   return rc;
@@ -1663,8 +1376,7 @@ int admm_node_update_rounds(admm_ctx* C, int tv_iters, void* stream) {
   const bool keep = (C->b.flags & ADMM_BATCH_KEEP_X) != 0;
   const bool reuse = keep && C->ats_valid;
   // a round count other than the bound one: enqueued directly (no recorded graph)
-  const int rc = C->dtype == ADMM_DTYPE_F32 ? enqueue_update_any<float>(C, s, reuse, tv_iters)
-                                            : enqueue_update_any<double>(C, s, reuse, tv_iters);
+  const int rc = enqueue_update_any(C, s, reuse, tv_iters);
   if (rc == ADMM_OK && keep) C->ats_valid = true;
   return rc;
 }
@@ -1673,8 +1385,8 @@ int admm_consensus(admm_ctx* C, void* stream) {
   if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
-  if (C->x_cons) {
-    HIPCHK(hipGraphLaunch(C->x_cons, s));
+  if (C->cons.x) {
+    HIPCHK(hipGraphLaunch(C->cons.x, s));
     return ADMM_OK;
   }
   return enqueue_consensus(C, s);
@@ -1685,15 +1397,13 @@ extern "C++" {
 // events around every in-solve launch of `kind` (0: the forward tap kernel of each CG step,
 // right after the CG / TV update that wrote p and p^T; 1: the back projector of each CG step,
 // right after its forward combine), exactly as in every replay; ms = their average duration.
-template <typename T>
-int time_in_solve(admm_ctx* C, int kind, hipStream_t s, float* ms) {
-  return with_vb(C->vb, [&](auto vbc) -> int {
+static int time_in_solve(admm_ctx* C, int kind, hipStream_t s, float* ms) {
+  return with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) -> int {
+    using T = typename decltype(tt)::type;
     constexpr int VB = decltype(vbc)::value;
     const int n = C->b.tv_iters * C->b.cg_iters;
-    std::vector<hipEvent_t> ev(2 * n);
-    // no system-scope fence (cache writeback / invalidation) at each record, which would
-    // perturb the launches they bracket
-    for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+    std::vector<Event> ev(2 * n);
+    for (Event& e : ev) RET(e.create());
     C->tf_ev = &ev;
     C->tf_next = 0;
     C->tf_kind = kind;
@@ -1705,24 +1415,23 @@ int time_in_solve(admm_ctx* C, int kind, hipStream_t s, float* ms) {
     if (rc == ADMM_OK && keep) C->ats_valid = true;
     if (rc == ADMM_OK && used == 0) rc = fail(ADMM_E_STATE, "no launch was timed");
     if (rc == ADMM_OK) {
-      HIPCHK(hipEventSynchronize(ev[used - 1]));
+      HIPCHK(hipEventSynchronize(ev[used - 1].e));
       float tot = 0.f;
       for (size_t i = 0; i < used; i += 2) {
         float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+        HIPCHK(hipEventElapsedTime(&t, ev[i].e, ev[i + 1].e));
         tot += t;
       }
       *ms = tot / (float)(used / 2);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     return rc;
   });
 }
 
-template <typename T>
-int time_fwd(admm_ctx* C, int reps, int in_solve, hipStream_t s, float* ms) {
-  if (in_solve) return time_in_solve<T>(C, 0, s, ms);
-  return with_vb(C->vb, [&](auto vbc) -> int {
+static int time_fwd(admm_ctx* C, int reps, int in_solve, hipStream_t s, float* ms) {
+  if (in_solve) return time_in_solve(C, 0, s, ms);
+  return with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) -> int {
+    using T = typename decltype(tt)::type;
     constexpr int VB = decltype(vbc)::value;
     // the forward tap kernel alone, back to back: k_fwdg (every sample tap) when grouped, else k_fwd
     auto one = [&]() -> int {
@@ -1731,17 +1440,15 @@ int time_fwd(admm_ctx* C, int reps, int in_solve, hipStream_t s, float* ms) {
                                   C->weighted ? (const T*)C->wS.p : nullptr);
     };
     RET(one());
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreateWithFlags(&e0, hipEventDisableSystemFence));
-    HIPCHK(hipEventCreateWithFlags(&e1, hipEventDisableSystemFence));
-    HIPCHK(hipEventRecord(e0, s));
+    Event e0, e1;
+    RET(e0.create());
+    RET(e1.create());
+    HIPCHK(hipEventRecord(e0.e, s));
     int rc = ADMM_OK;
     for (int i = 0; i < reps && rc == ADMM_OK; ++i) rc = one();
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIPCHK(hipEventRecord(e1.e, s));
+    HIPCHK(hipEventSynchronize(e1.e));
+    HIPCHK(hipEventElapsedTime(ms, e0.e, e1.e));
     return rc;
   });
 }
@@ -1753,8 +1460,7 @@ int admm_time_forward(admm_ctx* C, int reps, int in_solve, void* stream, double*
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
   float ms = 0.f;
-  RET(C->dtype == ADMM_DTYPE_F32 ? time_fwd<float>(C, reps, in_solve, s, &ms)
-                                  : time_fwd<double>(C, reps, in_solve, s, &ms));
+  RET(time_fwd(C, reps, in_solve, s, &ms));
   *ms_out = in_solve ? (double)ms : (double)ms / reps;
   return ADMM_OK;
 }
@@ -1776,7 +1482,7 @@ int admm_time_back(admm_ctx* C, void* stream, double* ms_out) {
   DEVICE_SCOPE(C->device);
   hipStream_t s = (hipStream_t)stream;
   float ms = 0.f;
-  RET(C->dtype == ADMM_DTYPE_F32 ? time_in_solve<float>(C, 1, s, &ms) : time_in_solve<double>(C, 1, s, &ms));
+  RET(time_in_solve(C, 1, s, &ms));
   *ms_out = (double)ms;
   return ADMM_OK;
 }
@@ -1792,11 +1498,11 @@ int admm_batch_info(admm_ctx* C, int* vb, int* mirror) {
 int admm_fwd_plan_info(admm_ctx* C, int plan, int* groups, int* blocks, double* staged, int* active) {
   if (!C || plan < 0 || plan >= admm_ctx::kPlans || !groups || !blocks || !staged || !active)
     return fail(ADMM_E_INVALID, "bad argument");
-  if (C->mm && C->half) C = C->half;  // mirror mode: the half geometry's plans are the bound ones
+  if (C->mm && C->half) C = C->half.get();  // mirror mode: the half geometry's plans are the bound ones
   *groups = C->plan_n[plan];
   *blocks = C->plan_blocks[plan];
   *staged = C->plan_staged[plan];
-  *active = (C->plan_n[plan] > 0 && C->groups == C->plan_groups[plan]) ? 1 : 0;
+  *active = (C->plan_n[plan] > 0 && C->groups == C->plan_groups(plan)) ? 1 : 0;
   return ADMM_OK;
 }
 

@@ -27,6 +27,8 @@
 
 #include <type_traits>
 
+#include "tables.hpp"
+
 namespace admm {
 
 constexpr int kBlock = 256;
@@ -35,30 +37,7 @@ constexpr int kFwdRays = 64;     // forward-projector block: 64 rays x 8 step se
 constexpr int kFwdSegs = 8;
 constexpr int kFwdBlock = kFwdRays * kFwdSegs;
 
-// Per-angle forward-projector constants (host-computed in float64).
-// Ray (t,k), step m:  l = A0 + k*A1 + m*dl  (interpolation coordinate).
-struct FwdAngle {
-  double A0, A1, dl;
-  double L;   // path length per step h/|alpha|
-  int caseA;  // 1: step over axis-1 index on the transposed image
-  int pad;
-};
-// Per-angle back-projector constants: fractional bin k_f = B0 + i*Bi + j*Bj,
-// weight(k) = max(0, 1 - |k-k_f|*slope) * L.
-struct BackAngle {
-  double B0, Bi, Bj;
-  double slope, L;
-};
-
-// Compact per-angle record of the back projector's hot loop (one s_load_dwordx8):
-// k_f = (i - c0) Bi + (j - c0) Bj + K with K = -det_min/hd - 1/2 the same for every
-// angle; float32 weights w0 = max(0, L - f sL), w1 = max(0, (L - sL) + f sL), formed
-// as one packed fma (f, f) * ws + wc with ws = (-sL, sL), wc = (L, L - sL).
-typedef float float2v __attribute__((ext_vector_type(2)));
-struct alignas(32) BackAngleC {
-  double Bi, Bj;
-  float2v ws, wc;
-};
+// (the angle records FwdAngle, BackAngle, BackAngleC and the forward plan tables: tables.hpp)
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
@@ -688,20 +667,9 @@ __global__ __launch_bounds__(kBlock) void k_csr_fwd(const int* __restrict__ ptr,
 #ifndef ADMM_FG_ROWS
 #define ADMM_FG_ROWS 4
 #endif
-#ifndef ADMM_FG_SEG
-#define ADMM_FG_SEG 8
-#endif
-#ifndef ADMM_FG_G
-#define ADMM_FG_G 16
-#endif
-#ifndef ADMM_FG_WIN
-#define ADMM_FG_WIN 256
-#endif
+// (ADMM_FG_SEG, ADMM_FG_G, ADMM_FG_WIN and kFgSeg, kFgG, kFgWin: tables.hpp, shared with the planner)
 constexpr int kFgRows = ADMM_FG_ROWS;  // rows staged per LDS chunk
-constexpr int kFgG = ADMM_FG_G;        // max angles (waves) per block
 constexpr int kFgThreads = 64 * kFgG;
-constexpr int kFgWin = ADMM_FG_WIN;    // staged window width (pixels)
-constexpr int kFgSeg = ADMM_FG_SEG;    // row segments (partial sums) per ray
 #ifndef ADMM_FG_DMA_ROWS
 #define ADMM_FG_DMA_ROWS 2  // rows per chunk of the LDS-DMA kernel (round 4: 4 rows 50.0 vs 51.2 us at C3, 28.2 vs 27.7 at 8 nodes)
 #endif
@@ -716,24 +684,6 @@ __device__ __forceinline__ int fg_ray_of_lane(int lane) {
   const int r = l < 4 ? l : l < 12 ? l + 12 : l < 16 ? l - 8 : l < 20 ? l + 8 : l < 28 ? l - 12 : l;
   return (lane & 32) + r;
 }
-
-// One angle group of the grouped forward projector: angles t0 .. t0+G-1 (one case).
-struct FgGroup {
-  int t0, G;
-};
-// The rays one block projects: angle t0+q of its group takes rays k0[q] .. k0[q]+nk[q]-1
-// (0 <= nk <= 64, inside [0, n_det)).  Every plan is a table of these (one per (group,
-// segment, chunk)); per (group, segment) the ranges of each angle partition its rays (less
-// any ray a clipped plan drops because it misses the segment inside the image).  The
-// 64-ray plans give angle q rays x*64 + delta_q + [0, 64), delta_q = 0 or the shift that
-// makes every angle of the group cross the same pixels at the segment's centre row; the
-// chunk-aligned plan starts every angle's chunk x at the same pixel of that row (a chunk
-// spans 64 rays of the group's densest angle, so sparser angles use fewer lanes), which
-// keeps the union window narrow far from the detector centre too.
-struct FgRange {
-  int k0[kFgG];
-  int nk[kFgG];
-};
 
 // The float forward keeps its tap weights in the units of its 32.32 fixed-point positions
 // (w1 = the fraction's low word as a float, w0 = 2^32 - w1: one VALU less per tap row than
