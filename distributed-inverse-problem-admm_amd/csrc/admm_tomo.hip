@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -280,6 +281,26 @@ int vb_for(int V, int dtype) {
   return dtype == ADMM_DTYPE_F64 ? std::min(vb, 4) : vb;
 }
 
+// A/B and test knobs of the environment (ADMM_BK_* are read when a context is created, ADMM_FWD_* when
+// a batch is bound).  env_choice: the value's first character as a digit in lo..hi; `unset` when the
+// variable is unset or empty, `other` for any other value.  env_word: 1 + the index of the word the
+// whole value equals, else 0.
+int env_choice(const char* name, int lo, int hi, int unset, int other) {
+  const char* v = getenv(name);
+  if (!v || !v[0]) return unset;
+  return (v[0] >= '0' + lo && v[0] <= '0' + hi) ? v[0] - '0' : other;
+}
+int env_choice(const char* name, int lo, int hi, int fallback) { return env_choice(name, lo, hi, fallback, fallback); }
+int env_word(const char* name, std::initializer_list<const char*> words) {
+  const char* v = getenv(name);
+  int i = 0;
+  for (const char* w : words) {
+    ++i;
+    if (v && std::string(v) == w) return i;
+  }
+  return 0;
+}
+
 void select_fwd_plan(admm_ctx* C, int pl) {
   C->groups = C->plan_groups(pl);
   C->rng = C->plan_rng(pl);
@@ -288,8 +309,8 @@ void select_fwd_plan(admm_ctx* C, int pl) {
 
 // Block table of plan pl for nch node chunks in launch order (fwd_plan.hpp fwd_block_order), uploaded
 int build_fwd_order_into(admm_ctx* C, int pl, int nch, int cus, Buf& buf, int* nblk) {
-  const char* mx = getenv("ADMM_FWD_MIRROR_XCD");  // "0": segment-per-XCD (A/B)
-  const std::vector<FgBlock> t = fwd_block_order(C->plans[pl], nch, cus, C->mirror_half, !(mx && mx[0] == '0'));
+  const bool mirror_xcd = env_choice("ADMM_FWD_MIRROR_XCD", 0, 0, 1) != 0;  // "0": segment-per-XCD (A/B)
+  const std::vector<FgBlock> t = fwd_block_order(C->plans[pl], nch, cus, C->mirror_half, mirror_xcd);
   RET(upload(buf, t));
   *nblk = (int)t.size();
   return ADMM_OK;
@@ -313,8 +334,7 @@ int pick_fwd_plan(admm_ctx* C, int nch, int* pl_out, int* cus_out, long* slots_o
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, C->device));
   if (per_cu < 1) return fail(ADMM_E_HIP, "grouped forward projector cannot be resident");
   const long slots = (long)per_cu * std::max(1, cus);
-  const char* f = getenv("ADMM_FWD_PLAN");
-  const int forced = (f && f[0] >= '0' && f[0] < '0' + admm_ctx::kPlans) ? f[0] - '0' : -1;
+  const int forced = env_choice("ADMM_FWD_PLAN", 0, admm_ctx::kPlans - 1, -1);
   *pl_out = choose_fwd_plan_index(C->plan_blocks, C->plan_n, C->plan_staged, nch, slots, forced);
   *cus_out = cus;
   if (slots_out) *slots_out = slots;
@@ -337,8 +357,7 @@ int choose_fwd_plan(admm_ctx* C, int V) {
   const int nch = (V + VB - 1) / VB;
   C->fg_cpb = 1;
   if constexpr (fwd_cpb2_ok<T, VB, MIRROR, VBR>()) {
-    const char* f = getenv("ADMM_FWD_CPB");
-    const int force = (f && f[0] >= '1' && f[0] <= '2') ? f[0] - '0' : 0;
+    const int force = env_choice("ADMM_FWD_CPB", 1, 2, 0);
     if (nch % 2 == 0 && force != 1) {
       int pl2 = 0, cus2 = 0;
       long slots2 = 0;
@@ -355,9 +374,7 @@ int choose_fwd_plan(admm_ctx* C, int V) {
   int pl = 0, cus = 0;
   RET((pick_fwd_plan<T, VB, MIRROR, VBR>(C, nch, &pl, &cus)));
   select_fwd_plan(C, pl);
-  return getenv("ADMM_FWD_NATURAL_ORDER") && getenv("ADMM_FWD_NATURAL_ORDER")[0] == '1'
-             ? build_fwd_order(C, pl, nch, 0)
-             : build_fwd_order(C, pl, nch, cus);
+  return build_fwd_order(C, pl, nch, env_choice("ADMM_FWD_NATURAL_ORDER", 1, 1, 0) ? 0 : cus);
 }
 
 template <typename F>
@@ -402,9 +419,7 @@ constexpr int mirror_vb() {
 // ADMM_FWD_MIRROR=0 / 1 forces it off / on.
 bool mirror_eligible(const admm_ctx* C) {
   if (C->csr || C->g.n_angles < 2 || C->g.n_angles % 2 != 0) return false;
-  const char* e = getenv("ADMM_FWD_MIRROR");
-  const bool want = (e && e[0]) ? e[0] == '1' : C->dtype == ADMM_DTYPE_F32;
-  if (!want) return false;
+  if (!env_choice("ADMM_FWD_MIRROR", 1, 1, C->dtype == ADMM_DTYPE_F32, 0)) return false;
   const double pi = 3.14159265358979323846;
   return std::fabs(C->g.angle_min) <= 1e-15 && std::fabs(C->g.angle_max - pi) <= 1e-12 &&
          std::fabs(C->g.det_min + C->g.det_max) <= 1e-12 * std::fabs(C->g.det_max);
@@ -452,6 +467,16 @@ int bind_fwd_plan(admm_ctx* C, int V) {
   return ADMM_OK;
 }
 
+// The optional trailing kernel argument of the weighted instantiations (kernels.hpp W...): f(wts) when
+// the batch has per-ray weights, else f()
+template <typename T, typename F>
+void with_weights(const T* wts, F&& f) {
+  if (wts)
+    f(wts);
+  else
+    f();
+}
+
 // wts: the bound batch's packed per-ray weights (the weighted instantiations) or null
 template <typename T, int VB, int MODE>
 int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, double* part, int V, hipStream_t s,
@@ -464,23 +489,26 @@ int launch_fwd(admm_ctx* C, const T* img, const T* imgT, T* sino, const T* b, do
     return ADMM_OK;
   }
   dim3 grid((C->g.n_det + kFwdRays - 1) / kFwdRays, C->g.n_angles, (V + VB - 1) / VB);
-  if (wts)
-    hipLaunchKernelGGL((k_fwd<T, VB, MODE, const T*>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang(),
-                       C->g.N, C->g.n_det, C->g.n_angles, V, wts);
-  else
-    hipLaunchKernelGGL((k_fwd<T, VB, MODE>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part, C->fang(), C->g.N,
-                       C->g.n_det, C->g.n_angles, V);
+  with_weights(wts, [&](auto... w) {
+    hipLaunchKernelGGL((k_fwd<T, VB, MODE, decltype(w)...>), grid, dim3(kFwdBlock), 0, s, img, imgT, sino, b, part,
+                       C->fang(), C->g.N, C->g.n_det, C->g.n_angles, V, w...);
+  });
   CHECK_LAUNCH();
   return ADMM_OK;
 }
 
 // hot-path forward projection of the bound batch: grouped kernel + fixed-order combine
-// the grouped forward projector's tap kernel (all sample taps; segment partials -> fpart)
-template <typename T, int VB>
-int launch_fwdg_taps_with(admm_ctx* C, const T* img, const T* imgT, T* fpart, const FgGroup* groups,
-                          const FgRange* rng, const int4* order, int nblk, int V, hipStream_t s) {
-  hipLaunchKernelGGL((k_fwdg<T, VB>), dim3(nblk), dim3(kFgThreads), 0, s, img, imgT, fpart, C->fang(), groups, rng,
-                     order, C->g.N, C->g.n_det, C->g.n_angles, V);
+// the grouped forward projector's tap kernel (all sample taps; segment partials -> fpart): kern over the
+// angles, groups and ranges of A (C itself, or in mirror mode its half geometry) and nblk blocks of `order`
+template <typename T>
+using FwdgKernel = void (*)(const T*, const T*, T*, const FwdAngle*, const FgGroup*, const FgRange*, const int4*, int,
+                            int, int, int);
+template <typename T>
+int launch_fwdg_taps_with(FwdgKernel<T> kern, admm_ctx* C, const admm_ctx* A, const T* img, const T* imgT, T* fpart,
+                          const FgGroup* groups, const FgRange* rng, const int4* order, int nblk, int V,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(kern, dim3(nblk), dim3(kFgThreads), 0, s, img, imgT, fpart, A->fang(), groups, rng, order,
+                     C->g.N, C->g.n_det, A->g.n_angles, V);
   CHECK_LAUNCH();
   return ADMM_OK;
 }
@@ -492,25 +520,17 @@ int launch_fwdg_taps(admm_ctx* C, const T* img, const T* imgT, int V, hipStream_
     const int nchv = ((V + VB - 1) / VB) * (VB / MH);
     const admm_ctx* H = C->half.get();
     if (nchv != H->fg_order_nch) return fail(ADMM_E_STATE, "mirror block table built for another batch size");
+    FwdgKernel<T> kern = k_fwdg<T, VBV, true, VB>;
     if constexpr (fwd_cpb2_ok<T, VBV, true, VB>()) {
-      if (H->fg_cpb == 2) {  // two virtual chunks per block (the table holds chunk pairs)
-        hipLaunchKernelGGL((k_fwdg<T, VBV, true, VB, 2>), dim3(H->fg_nblk), dim3(kFgThreads), 0, s, img, imgT,
-                           (T*)C->fpart.p, H->fang(), H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N,
-                           C->g.n_det, H->g.n_angles, nchv * VBV);
-        CHECK_LAUNCH();
-        return ADMM_OK;
-      }
+      if (H->fg_cpb == 2) kern = k_fwdg<T, VBV, true, VB, 2>;  // two virtual chunks per block (the table holds pairs)
     }
-    hipLaunchKernelGGL((k_fwdg<T, VBV, true, VB>), dim3(H->fg_nblk), dim3(kFgThreads), 0, s, img, imgT,
-                       (T*)C->fpart.p, H->fang(), H->groups, H->rng, (const int4*)H->fg_order.p, C->g.N, C->g.n_det,
-                       H->g.n_angles, nchv * VBV);
-    CHECK_LAUNCH();
-    return ADMM_OK;
+    return launch_fwdg_taps_with<T>(kern, C, H, img, imgT, (T*)C->fpart.p, H->groups, H->rng,
+                                    (const int4*)H->fg_order.p, H->fg_nblk, nchv * VBV, s);
   }
   const int nch = (V + VB - 1) / VB;
   if (nch != C->fg_order_nch) return fail(ADMM_E_STATE, "forward block table built for another batch size");
-  return launch_fwdg_taps_with<T, VB>(C, img, imgT, (T*)C->fpart.p, C->groups, C->rng,
-                                      (const int4*)C->fg_order.p, C->fg_nblk, V, s);
+  return launch_fwdg_taps_with<T>(k_fwdg<T, VB>, C, C, img, imgT, (T*)C->fpart.p, C->groups, C->rng,
+                                  (const int4*)C->fg_order.p, C->fg_nblk, V, s);
 }
 
 template <typename T, int VB, int MODE>
@@ -538,22 +558,18 @@ int launch_fwd_batch(admm_ctx* C, const T* img, const T* imgT, T* sino, const T*
     // MODE 0: two threads per virtual ray (k_fwd_combine_mirror); MODE 1: one (its block partials)
     const size_t mthreads = (size_t)mh * (MODE == 0 ? 2 : 1);
     dim3 mg((unsigned)((mthreads + kBlock - 1) / kBlock), nch * (VB / MH));
-    if (wts)
-      hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE, const T*>), mg, dim3(kBlock), 0, s,
-                         (const T*)C->fpart.p, sino, b, part, C->half->fang(), C->g.n_det, C->half->g.n_angles, V, wts);
-    else
-      hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE>), mg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino,
-                         b, part, C->half->fang(), C->g.n_det, C->half->g.n_angles, V);
+    with_weights(wts, [&](auto... w) {
+      hipLaunchKernelGGL((k_fwd_combine_mirror<T, VBV, VB, MODE, decltype(w)...>), mg, dim3(kBlock), 0, s,
+                         (const T*)C->fpart.p, sino, b, part, C->half->fang(), C->g.n_det, C->half->g.n_angles, V, w...);
+    });
     CHECK_LAUNCH();
     return ADMM_OK;
   }
   dim3 cg((C->mrays + kBlock - 1) / kBlock, nch);
-  if (wts)
-    hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE, const T*>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
-                       C->fang(), C->g.n_det, C->g.n_angles, V, wts);
-  else
-    hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b, part,
-                       C->fang(), C->g.n_det, C->g.n_angles, V);
+  with_weights(wts, [&](auto... w) {
+    hipLaunchKernelGGL((k_fwd_combine<T, VB, MODE, decltype(w)...>), cg, dim3(kBlock), 0, s, (const T*)C->fpart.p, sino, b,
+                       part, C->fang(), C->g.n_det, C->g.n_angles, V, w...);
+  });
   CHECK_LAUNCH();
   return ADMM_OK;
 }
@@ -961,8 +977,8 @@ int op_forward_chunk(admm_ctx* C, const T* img, T* sino, int nc, hipStream_t s) 
   CHECK_LAUNCH();
   hipLaunchKernelGGL((k_transpose<T, VB>), tile_grid(C, 1, VB), dim3(kBlock), 0, s, (const T*)xs, xsT, C->g.N);
   CHECK_LAUNCH();
-  RET((launch_fwdg_taps_with<T, VB>(C, xs, xsT, (T*)C->op_fpart.p, C->plan_groups(pl), C->plan_rng(pl),
-                                    (const int4*)C->op_order[pl].p, C->op_nblk[pl], nc, s)));
+  RET((launch_fwdg_taps_with<T>(k_fwdg<T, VB>, C, C, xs, xsT, (T*)C->op_fpart.p, C->plan_groups(pl), C->plan_rng(pl),
+                                (const int4*)C->op_order[pl].p, C->op_nblk[pl], nc, s)));
   hipLaunchKernelGGL((k_fwd_combine<T, VB, 0>), dim3((m + kBlock - 1) / kBlock, 1), dim3(kBlock), 0, s,
                      (const T*)C->op_fpart.p, sI, (const T*)nullptr, (double*)nullptr, C->fang(), C->g.n_det,
                      C->g.n_angles, nc);
@@ -1023,13 +1039,8 @@ int admm_ctx_create(admm_ctx** out, const admm_geom* geom, int dtype, int max_im
   C->g = g;
   C->dtype = dtype;
   C->device = device;
-  {
-    const char* st = getenv("ADMM_BK_STAGING");
-    const std::string v = st ? st : "";
-    C->bk_staging = v == "reg" ? 1 : v == "dma1" ? 2 : v == "dma2" ? 3 : 0;
-    const char* ep = getenv("ADMM_BK_EPI");
-    C->bk_epi_lds = !(ep && std::string(ep) == "global");
-  }
+  C->bk_staging = env_word("ADMM_BK_STAGING", {"reg", "dma1", "dma2"});
+  C->bk_epi_lds = env_word("ADMM_BK_EPI", {"global"}) == 0;
   HIPCHK(hipDeviceGetAttribute(&C->n_cu, hipDeviceAttributeMultiprocessorCount, device));
   C->max_images = max_images;
   C->npix = g.N * g.N;

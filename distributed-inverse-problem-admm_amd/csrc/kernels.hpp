@@ -459,6 +459,43 @@ __device__ __forceinline__ const T* wt_ptr() { return nullptr; }
 template <typename T>
 __device__ __forceinline__ const T* wt_ptr(const T* w) { return w; }
 
+// The sinogram epilogue -- the data term -- of one lane of k_fwd, k_csr_fwd and k_fwd_combine
+// (k_fwd_combine_mirror writes the same rule out for its two angles per thread: a change here is made
+// there as well).  s: the lane's ray sum; SCALE: s *= L first.  MODE 0: s *= omega (WT).  MODE 1, a
+// lane that holds a node (live): s -= b[bi], sq = s^2 in float64, then (WT) sq = omega sq and
+// s = omega s; a padding lane's s = 0 and its sq stays as the caller set it (0).  w is read only if WT.
+template <typename T, int MODE, bool WT, bool SCALE = true>
+__device__ __forceinline__ void sino_finish(T& s, T L, const T* __restrict__ b, size_t bi, T w, bool live, double& sq) {
+  if constexpr (SCALE) s = s * L;
+  if (MODE == 1) {
+    if (live) {
+      s = s - b[bi];
+      sq = (double)s * (double)s;
+      if constexpr (WT) {
+        sq = (double)w * sq;
+        s = w * s;
+      }
+    } else {
+      s = T(0);
+    }
+  } else if constexpr (WT) {
+    s = s * w;
+  }
+}
+
+// MODE 1's ||s||^2 partials of a kBlock-thread block: sq summed over the block (block_reduce's
+// fixed order), one value per node and block to part[node][block]
+template <int NU>
+__device__ __forceinline__ void sq_partials_out(double (&sq)[NU], int v0, int nv, double* __restrict__ part) {
+  __shared__ double lds[4 * NU];
+  block_reduce<NU>(sq, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (u < nv) part[(size_t)(v0 + u) * gridDim.x + blockIdx.x] = sq[u];
+  }
+}
+
 template <typename T, int VB, int MODE, typename... W>
 __global__ __launch_bounds__(kFwdBlock) void k_fwd(const T* __restrict__ img, const T* __restrict__ imgT,
                                                 T* __restrict__ sino, const T* __restrict__ bsino,
@@ -550,23 +587,9 @@ __global__ __launch_bounds__(kFwdBlock) void k_fwd(const T* __restrict__ img, co
     if constexpr (WT) gload<T, VB>(wts + ((size_t)chunk * n_ang * n_det + ray) * VB, w);
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
-      s[u] = (((red[0][u][lane] + red[1][u][lane]) + (red[2][u][lane] + red[3][u][lane])) +
-              ((red[4][u][lane] + red[5][u][lane]) + (red[6][u][lane] + red[7][u][lane]))) *
-             (T)a.L;
-      if (MODE == 1) {
-        if (u < nv) {
-          s[u] = s[u] - bsino[(size_t)(v0 + u) * n_ang * n_det + ray];
-          sq[u] = (double)s[u] * (double)s[u];
-          if constexpr (WT) {
-            sq[u] = (double)w[u] * sq[u];
-            s[u] = w[u] * s[u];
-          }
-        } else {
-          s[u] = T(0);
-        }
-      } else if constexpr (WT) {
-        s[u] = s[u] * w[u];
-      }
+      s[u] = ((red[0][u][lane] + red[1][u][lane]) + (red[2][u][lane] + red[3][u][lane])) +
+             ((red[4][u][lane] + red[5][u][lane]) + (red[6][u][lane] + red[7][u][lane]));
+      sino_finish<T, MODE, WT>(s[u], (T)a.L, bsino, (size_t)(v0 + u) * n_ang * n_det + ray, w[u], u < nv, sq[u]);
     }
     gstore<T, VB>(sino + ((size_t)chunk * n_ang * n_det + ray) * VB, s);
   }
@@ -618,28 +641,12 @@ __global__ __launch_bounds__(kBlock) void k_csr_fwd(const int* __restrict__ ptr,
 #pragma unroll
       for (int u = 0; u < VB; ++u) acc[u] = fma(w, pv[u], acc[u]);
     }
-    if (MODE == 1) {
 #pragma unroll
-      for (int u = 0; u < VB; ++u) {
-        if (u < nv) {
-          acc[u] = acc[u] - bsino[(size_t)(v0 + u) * m + row];
-          sq[u] = (double)acc[u] * (double)acc[u];
-        } else {
-          acc[u] = T(0);
-        }
-      }
-    }
+    for (int u = 0; u < VB; ++u)  // (no L, no weights)
+      sino_finish<T, MODE, false, false>(acc[u], T(1), bsino, (size_t)(v0 + u) * m + row, T(1), u < nv, sq[u]);
     gstore<T, VB>(sino + ((size_t)chunk * m + row) * VB, acc);
   }
-  if (MODE == 1) {
-    __shared__ double lds[4 * VB];
-    block_reduce<VB>(sq, lds);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int u = 0; u < VB; ++u)
-        if (u < nv) part[(size_t)(v0 + u) * gridDim.x + blockIdx.x] = sq[u];
-    }
-  }
+  if (MODE == 1) sq_partials_out<VB>(sq, v0, nv, part);
 }
 
 // ===========================================================================
@@ -1200,34 +1207,11 @@ __global__ __launch_bounds__(kBlock) void k_fwd_combine(const T* __restrict__ pa
       for (int u = 0; u < VB; ++u) acc[u] += pv[u];
     }
 #pragma unroll
-    for (int u = 0; u < VB; ++u) {
-      acc[u] *= L;
-      if (MODE == 1) {
-        if (u < nv) {
-          acc[u] -= bsino[(size_t)(v0 + u) * m_rays + ray];
-          sq[u] = (double)acc[u] * (double)acc[u];
-          if constexpr (WT) {
-            sq[u] = (double)w[u] * sq[u];
-            acc[u] = w[u] * acc[u];
-          }
-        } else {
-          acc[u] = T(0);
-        }
-      } else if constexpr (WT) {
-        acc[u] *= w[u];
-      }
-    }
+    for (int u = 0; u < VB; ++u)
+      sino_finish<T, MODE, WT>(acc[u], L, bsino, (size_t)(v0 + u) * m_rays + ray, w[u], u < nv, sq[u]);
     gstore<T, VB>(sino + ((size_t)chunk * m_rays + ray) * VB, acc);
   }
-  if (MODE == 1) {
-    __shared__ double lds[4 * VB];
-    block_reduce<VB>(sq, lds);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int u = 0; u < VB; ++u)
-        if (u < nv) pout[(size_t)(v0 + u) * gridDim.x + blockIdx.x] = sq[u];
-    }
-  }
+  if (MODE == 1) sq_partials_out<VB>(sq, v0, nv, pout);
 }
 
 // The mirror-mode combine (k_fwdg<..., MIRROR>): virtual chunk c' of the half geometry's rays

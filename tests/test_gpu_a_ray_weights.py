@@ -108,6 +108,28 @@ def test_weighted_update_through_the_ungrouped_forward(cuda, monkeypatch, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+def test_unweighted_update_through_the_ungrouped_forward(cuda, monkeypatch, dtype):
+    """The same batch without weights: the unweighted k_fwd (MODE 0 in the CG, MODE 1 for the residual and
+    its statistics) against the unweighted oracle, with the same bars."""
+    case = wr.KFWD_CASE
+    _set_mirror(monkeypatch, case.mirror)
+    P = wr.case_problem(case, dtype, wr.KFWD_DWF)
+    nb = _batch(case, dtype, P, None, dwf=wr.KFWD_DWF)
+    assert nb.fwd_plans() == [] and not nb.mirror
+    st = sr.random_state(nb, case.seed)
+    nb.node_update()
+    got = _read(nb)
+
+    def run(A, dt):
+        return sr.oracle_update(st, P["plan"], A, P["b"], P["q_fn"], P["prm"], case.fusion, dtype=dt, phantom=P["ph"])
+
+    ref = run(P["A"], np.float64)
+    bars, yard = _bars(case, dtype, P, ref, lambda: run(sr.as_f32_matrix(P["A"]), np.float32))
+    _compare(dtype + " k_fwd", case, dtype, got, ref, bars, yard)
+    _untouched(nb, st)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", wr.WEIGHT_REUSE_CASES, ids=sr.case_id)
 def test_weighted_reuse_start(cuda, monkeypatch, case, dtype):
     """ADMM_BATCH_KEEP_X: the second update starts from the first one's A^T W (A x - b)."""
