@@ -129,6 +129,9 @@ SYMBOLS = {
     "admm_image_metrics_work": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
     "admm_batch_set_ray_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
     "admm_column_norms_sq_weighted": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_bound_project": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                           C.c_double, C.c_double, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_bound_project_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
 }
 
 _lock = threading.Lock()

@@ -38,6 +38,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .bounds import BOUND_KEYS, BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
 from .exchange import split_stats
 from .fbp import FILTERS, fbp
 from .geometry import CSR_WEIGHTS_MSG, RayTransform
@@ -92,8 +93,23 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
              pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
-             metrics_mask=None, ray_weights=None):
-    """``ray_weights``: per-ray weights omega of the data term, 1/2 sum_r omega_r (A x - b)_r^2
+             metrics_mask=None, bounds=None, bound_weight=None, return_feasible=False, ray_weights=None):
+    """``bounds``: None or (lo, hi): the box lo <= x_i <= hi on every node's image; each of lo, hi is
+    None (that side off), a scalar, or an (N, N) / (n,) array shared by all nodes (a support mask is
+    hi = 0 outside the support); NaN and lo > hi anywhere raise ValueError on the host.  Node i gets
+    the splitting x_i = w_i, w_i in the box: one more quadratic term (rho / 2) ||x_i - (w_i - f_i)||^2
+    weighted by q_c,i = ``bound_weight`` * Wi_list[i] (kappa, default 1, > 0) in its x-update, and after
+    the edge updates w_i = clip(x_i + f_i), f_i += x_i - w_i (admm_bound_project; exact in the limit,
+    rank-local).  The history gains ``bound_primal`` = sqrt(sum_i |x_i - w_i|^2), ``bound_dual`` =
+    rho sqrt(sum_i |w_i - w_i_old|^2), ``bound_violation`` = sqrt(sum_i |x_i - clip(x_i)|^2) and the
+    per-node arrays ``bound_pri_per_node`` / ``bound_violation_per_node`` (the sums, not their roots);
+    ``primal`` and ``dual`` keep the reference's edge-only definition; the stop test additionally
+    requires bound_primal < eps_pri and bound_dual < eps_dual; ``obj_per_node`` / ``obj_total`` then
+    include the constraint's quadratic term (ADMM_NODE_STAT_QUAD: it is part of the node's
+    subproblem).  Needs stored z and fusion="midpoint" (ValueError otherwise, on every rank alike).
+    ``return_feasible=True`` returns w_i, inside the box exactly, instead of x_i.  With bounds=None
+    nothing changes: no slot, no launch, no table column, no history key.
+    ``ray_weights``: per-ray weights omega of the data term, 1/2 sum_r omega_r (A x - b)_r^2
     (weighted least squares; omega = 0 masks a ray): None, one (m,) / (angles, det) array for every
     node, or one entry (array, tensor or None) per graph node; finite and >= 0, checked on the host
     before any device work; geometry operators only.  ``sino_mse`` then records the weighted sum.
@@ -137,6 +153,11 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         tv_iters = inner_chunks[0]
     # argument errors on every rank alike, before any operator is built on the device
     metrics = _check_metric_args(metrics, data_range, metrics_mask, phantom_true, N)
+    bounds = check_bounds(bounds, N)
+    bound_weight = check_bound_weight(bound_weight, bounds)
+    check_bound_run(bounds, fusion, edge_state, os.environ.get("ADMM_EDGE_STATE", ""))
+    if return_feasible and bounds is None:
+        raise ValueError("return_feasible needs bounds=(lo, hi)")
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through
@@ -162,7 +183,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                     tv_iters, cg_iters, tv_kind, phantom_true, fusion=fusion, Wi_list=Wi_list,
                     keep_x=inner_tol is None, group=group, streams=streams,  # this loop never writes x itself
                     derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state],
-                    ray_weights=ray_weights)
+                    ray_weights=ray_weights, bounds=bounds, bound_weight=bound_weight if bounds is not None else None)
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
     if start is not None:
@@ -174,6 +195,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     hist = {k: [] for k in HISTORY_KEYS + EXTRA_KEYS}
     for name in metrics or ():
         hist[f"{name}_per_node"], hist[f"{name}_mean"] = [], []
+    if bounds is not None:
+        hist.update({k: [] for k in BOUND_KEYS})
     edges = plan.edges
     have_ph = phantom_true is not None
     if verbose and rank == 0:
@@ -221,22 +244,22 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             dev_hist[k - flushed].copy_(flat)
             if k + 1 - flushed == dev_hist.shape[0]:  # block full: flush to the host
                 flushed = _flush_pipelined(hist, dev_hist, flushed, k + 1, rg, V_total, edges, rho, lam_tv,
-                                           have_ph, verbose and rank == 0, metrics)
+                                           have_ph, verbose and rank == 0, metrics, bounds is not None)
             continue
         ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))
-        pn, dn = _record(hist, _take_metrics(hist, metrics, ns.numpy()), es.numpy(), edges, V_total, rho, lam_tv,
-                         et, have_ph)
+        ns, bres = _take_bounds(hist, bounds is not None, _take_metrics(hist, metrics, ns.numpy()), rho)
+        pn, dn = _record(hist, ns, es.numpy(), edges, V_total, rho, lam_tv, et, have_ph)
         if snapshot_dir is not None and ((k + 1) % snapshot_every == 0):
             _snapshot(snapshot_dir, k, rg, N)
         if verbose and rank == 0 and k % 10 == 0:
             print(f"iter {k}, primal {pn:.3e}, dual {dn:.3e}")
-        if pn < eps_pri and dn < eps_dual:
+        if pn < eps_pri and dn < eps_dual and (bres is None or (bres[0] < eps_pri and bres[1] < eps_dual)):
             if verbose and rank == 0:
                 print(f"stopped at iter {k}, primal {pn:.3e}, dual {dn:.3e}")
             break
     if pipelined and dev_hist is not None and iters_done > flushed:
         flushed = _flush_pipelined(hist, dev_hist, flushed, iters_done, rg, V_total, edges, rho, lam_tv, have_ph,
-                                   verbose and rank == 0, metrics)
+                                   verbose and rank == 0, metrics, bounds is not None)
     torch.cuda.synchronize()
     if timing is not None:
         import time
@@ -247,7 +270,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         _write_params(snapshot_dir, rho, lam_tv, V_total, mu, tv_iters, cg_iters)
     if inspect is not None:
         inspect(rg)
-    X = rg.images()
+    X = rg.images(feasible=bool(return_feasible))
     if return_tensors:
         return [X[i] for i in range(V_total)], hist
     Xh = X.to("cpu").numpy()
@@ -329,15 +352,35 @@ def _take_metrics(hist, metrics, ns):
     return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1)
 
 
-def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None):
+def _take_bounds(hist, bounded, ns, rho):
+    """Record the projection's three sums (the columns right after the library's node statistics
+    once the metric columns are taken) of one iteration's node table; returns the table without
+    them and (bound_primal, bound_dual), or (ns, None) for a run without bounds."""
+    if not bounded:
+        return ns, None
+    c0, c1 = _NODE_STATS, _NODE_STATS + BOUND_STATS
+    r2, dw2, viol = (ns[:, c0 + j].copy() for j in range(BOUND_STATS))
+    bp = math.sqrt(float(np.sum(r2)))
+    bd = rho * math.sqrt(float(np.sum(dw2)))  # the form _record uses for ``dual``
+    hist["bound_primal"].append(bp)
+    hist["bound_dual"].append(bd)
+    hist["bound_violation"].append(math.sqrt(float(np.sum(viol))))
+    hist["bound_pri_per_node"].append(r2)
+    hist["bound_violation_per_node"].append(viol)
+    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), (bp, bd)
+
+
+def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None,
+                     bounded=False):
     """Record iterations k0 .. k1-1 of the pipelined statistics (rows 0 .. k1-k0-1 of
     ``dev_hist``) on the host; returns k1."""
     host = dev_hist[: k1 - k0].to("cpu")
-    nsw = rg.batches[0].node_stats.shape[1] + len(metrics or ())
+    nsw = rg.node_stat_width
     extra = np.stack([np.full(V_total, np.nan), np.ones(V_total)], axis=1)
     for k in range(k0, k1):
         ns, es = split_stats(host[k - k0], V_total, nsw, len(edges), rg.batches[0].edge_stats.shape[1])
-        pn, dn = _record(hist, np.concatenate([_take_metrics(hist, metrics, ns.numpy()), extra], axis=1), es.numpy(),
+        ns, _ = _take_bounds(hist, bounded, _take_metrics(hist, metrics, ns.numpy()), rho)
+        pn, dn = _record(hist, np.concatenate([ns, extra], axis=1), es.numpy(),
                          edges, V_total, rho, lam_tv, eps_target(k), have_ph)
         if verbose and k % 10 == 0:
             print(f"iter {k}, primal {pn:.3e}, dual {dn:.3e}")

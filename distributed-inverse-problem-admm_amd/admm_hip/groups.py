@@ -32,6 +32,7 @@ from .exchange import HaloExchange, assemble_stats_device, assemble_stats_parts,
 import torch.distributed as dist
 
 from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, z_is_stored
+from .bounds import check_bound_run, check_bound_weight, check_bounds
 from .solver import NodeBatch
 
 
@@ -94,21 +95,23 @@ def rank_batches(A_list, plan: ShardPlan, streams: int = 1):
     return [(k, members[k]) for k in keys]
 
 
-def stored_edges_per_rank(A_list, G, V_total: int, world: int, streams: int = 1) -> list[int]:
+def stored_edges_per_rank(A_list, G, V_total: int, world: int, streams: int = 1, bound_slots: bool = False) -> list[int]:
     """Stored edge slots of every rank of a ``world``-rank run, summed over each rank's device
-    batches (rank_batches) -- what the stored-z rule (plan.z_is_stored) weighs."""
+    batches (rank_batches) -- what the stored-z rule (plan.z_is_stored) weighs.  ``bound_slots``:
+    a run with bound constraints stores one more (w, f) row pair per local node."""
     out = []
     for r in range(world):
         pr = make_plan(G, V_total, world, r)
         if not pr.local_nodes:
             out.append(0)
             continue
+        extra = len(pr.local_nodes) if bound_slots else 0
         bs = rank_batches(A_list, pr, streams)
         if len(bs) == 1:
-            out.append(len(pr.stored_edges))
+            out.append(len(pr.stored_edges) + extra)
         else:
             out.append(sum(len(make_subset_plan(G, V_total, nodes, world, r, pr.ranges, pr.edges).stored_edges)
-                           for _, nodes in bs))
+                           for _, nodes in bs) + extra)
     return out
 
 
@@ -135,8 +138,13 @@ def run_hbm_bytes(device, world: int, group=None, collective: bool = True) -> in
 class RankGroups:
     def __init__(self, A_list, G, V_total: int, world: int, rank: int, sinograms, Qij_diag_fn,
                  rho, lam, mu, tv_iters, cg_iters, tv_kind, phantom, fusion="midpoint", Wi_list=None,
-                 keep_x=False, group=None, halo=True, streams=1, derive_z=None, ray_weights=None):
-        """``ray_weights``: per-ray weights of the data term by global node (solver.node_ray_weights);
+                 keep_x=False, group=None, halo=True, streams=1, derive_z=None,
+                 bounds=None, bound_weight=None, ray_weights=None):
+        """``bounds`` / ``bound_weight``: the box lo <= x <= hi on every image and kappa of
+        q_c,i = kappa * Wi_list[i] (NodeBatch; bounds.check_bounds).  They need stored z and midpoint
+        fusion: derived z -- forced, or chosen by the HBM rule, which counts the V extra rows -- and
+        weighted fusion raise ValueError, from run-global facts and so on every rank alike.
+        ``ray_weights``: per-ray weights of the data term by global node (solver.node_ray_weights);
         every batch takes its own nodes' entries.  ``halo=False``: no inter-rank exchange (bench.py's per-rank proxy: one rank's share
         of a ``world``-rank run on one GPU, its halo rows held fixed).  ``streams`` > 1: every
         operator group of at least 2 x SPLIT_MIN nodes is split into up to that many near-equal
@@ -148,6 +156,10 @@ class RankGroups:
         stored edges) unless ADMM_EDGE_STATE=stored|derived forces it; True / False force
         derived / stored z."""
         self.plan: ShardPlan = make_plan(G, V_total, world, rank)
+        self.bounds = check_bounds(bounds, A_list[0].geom.N) if bounds is not None else None
+        check_bound_weight(bound_weight, self.bounds)
+        forced = os.environ.get("ADMM_EDGE_STATE", "")
+        check_bound_run(self.bounds, fusion, {None: None, True: "derived", False: "stored"}[derive_z], forced)
         if not self.plan.local_nodes:
             raise ValueError(f"rank {rank} owns no graph nodes ({V_total} nodes over {world} ranks)")
         self.world = world
@@ -172,11 +184,14 @@ class RankGroups:
         keys = [k for k, _ in bs]
         members = dict(bs)
         self.fusion = fusion
-        forced = os.environ.get("ADMM_EDGE_STATE", "")
         if derive_z is None and forced in ("stored", "derived"):
             derive_z = forced == "derived"
         if derive_z is None and fusion == "midpoint":
-            derive_z = not z_is_stored(stored_edges_per_rank(A_list, G, V_total, world, streams), n0, hbm, fusion)
+            derive_z = not z_is_stored(stored_edges_per_rank(A_list, G, V_total, world, streams,
+                                                             bound_slots=self.bounds is not None), n0, hbm, fusion)
+            if derive_z and self.bounds is not None:
+                raise ValueError("bounds need stored z, and this run's edge state (the V constraint rows "
+                                 "included) does not fit the stored-z rule (plan.z_is_stored)")
         self.derive_z = bool(derive_z) if derive_z is not None else False
         devices = {k[0][2] for k in keys}
         if len(devices) > 1:
@@ -192,7 +207,8 @@ class RankGroups:
             geom, dtype, device = k[0]
             self.batches.append(NodeBatch(geom, dtype, gp, sinograms, Qij_diag_fn, rho, lam, mu, tv_iters,
                                           cg_iters, tv_kind, phantom, device, fusion=fusion, Wi_list=Wi_list,
-                                          keep_x=keep_x, derive_z=self.derive_z, ray_weights=ray_weights))
+                                          keep_x=keep_x, derive_z=self.derive_z, ray_weights=ray_weights,
+                                          bounds=self.bounds, bound_weight=bound_weight))
         self.device = self.batches[0].dev
         if len(self.batches) == 1:
             self.x_rank = self.batches[0].x_ext
@@ -266,11 +282,12 @@ class RankGroups:
     @property
     def overlaps_exchange(self) -> bool:
         """exchange_consensus can run the rank-internal edge updates under the halo exchange:
-        one batch, stored z, midpoint fusion, an inter-rank exchange, and internal edges."""
+        one batch, stored z, midpoint fusion, an inter-rank exchange, and internal edges (or the
+        bound projection, which needs no halo row either)."""
         if self.halo is None or not self.halo.active or not self.single:
             return False
         nb = self.batches[0]
-        return nb.z is not None and nb.fusion == "midpoint" and nb.plan.n_internal > 0
+        return nb.z is not None and nb.fusion == "midpoint" and (nb.plan.n_internal > 0 or nb.bounds is not None)
 
     def exchange_consensus(self) -> None:
         """``exchange()`` then ``consensus()``, with the edges whose endpoints are both local
@@ -285,6 +302,8 @@ class RankGroups:
         nb = self.batches[0]
         h = self.halo.start()
         nb.consensus_range(0, nb.plan.n_internal, nb.V)
+        if nb.bounds is not None:
+            nb.bound_project()  # rank-local: with the internal edges, under the exchange
         self.halo.finish(h)
         nb.consensus_range(nb.plan.n_internal, len(nb.plan.stored_edges), nb.plan.n_xext)
 
@@ -306,10 +325,20 @@ class RankGroups:
         self._concurrent(score)
 
     def _node_stats(self, nb):
-        """The batch's node-statistics rows, widened by its metric columns when metrics are on."""
+        """The batch's node-statistics rows, widened by its metric columns when metrics are on and
+        then by the projection's three sums when the run has bounds."""
+        cols = [nb.node_stats]
         if self.metric_names:
-            return torch.cat([nb.node_stats, nb.metric_cols], 1)
-        return nb.node_stats
+            cols.append(nb.metric_cols)
+        if self.bounds is not None:
+            cols.append(nb.bound_stats)
+        return torch.cat(cols, 1) if len(cols) > 1 else nb.node_stats
+
+    @property
+    def node_stat_width(self) -> int:
+        """Columns of the node table ``stats_device`` assembles."""
+        return (self.batches[0].node_stats.shape[1] + len(self.metric_names)
+                + (self.batches[0].bound_stats.shape[1] if self.bounds is not None else 0))
 
     def stats(self, extra=None):
         """Global node / edge statistics; ``extra`` (rank-local [V, k] numpy, rows in
@@ -337,6 +366,11 @@ class RankGroups:
             out.extend((g, nb.x_local[r]) for r, g in enumerate(nb.plan.local_nodes))
         return sorted(out, key=lambda t: t[0])
 
-    def images(self) -> torch.Tensor:
+    def images(self, feasible: bool = False) -> torch.Tensor:
+        """Every node's image x_i; ``feasible`` (a run with bounds): its constraint copy w_i, which
+        lies in the box exactly."""
+        if feasible and self.bounds is None:
+            raise ValueError("feasible images need bounds")
         return gather_images_parts(self.plan.V_total, self.world,
-                                   [(nb.plan, nb.x_local) for nb in self.batches], self.group)
+                                   [(nb.plan, nb.w_bound if feasible else nb.x_local) for nb in self.batches],
+                                   self.group)

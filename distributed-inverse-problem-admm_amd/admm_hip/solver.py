@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .bounds import BoundProjector, check_bound_weight, check_bounds
 from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
                        ray_weights_host, _Ctx)
 from .plan import ShardPlan, z_is_stored
@@ -60,8 +61,19 @@ class NodeBatch:
                  Qij_diag_fn, rho: float, lam: float, mu: float, tv_iters: int = 10,
                  cg_iters: int = 5, tv_kind: str = "iso", phantom=None, device: int = 0,
                  fusion: str = "midpoint", Wi_list=None, keep_x: bool = False, derive_z: bool | None = None,
-                 ray_weights=None):
-        """``ray_weights``: per-ray weights omega of the data term 1/2 sum_r omega_r (A x - b)_r^2
+                 bounds=None, bound_weight=None, ray_weights=None):
+        """``bounds``: None or (lo, hi) (bounds.check_bounds): the box lo <= x <= hi on every local
+        image through the splitting x_k = w_k, w_k in the box.  The plan stays as it is; local node k
+        gets one more incidence after its real ones -- edge slot E + k (``z[E + k]`` = w_k,
+        ``y[E + k]`` = the scaled dual f_k, sign +1, edge_a = edge_b = k) with the q slot
+        ``n_qslots + k`` holding q_c,k = ``bound_weight`` * Wi_list[g] (kappa, default 1) -- so the
+        unchanged x-update reads it like an edge term, D includes q_c, the QUAD statistic includes
+        the constraint's quadratic term (it is part of the node's subproblem), and the batch is bound
+        with n_edges = E + V.  ``consensus`` then updates the real edges (admm_consensus_range) and
+        projects (admm_bound_project -> ``bound_stats``); admm_consensus never sees the extra slots.
+        Needs stored z and midpoint fusion.  None: nothing changes.
+
+        ``ray_weights``: per-ray weights omega of the data term 1/2 sum_r omega_r (A x - b)_r^2
         (node_ray_weights: None, one array for every node, or a per-global-node sequence; finite,
         >= 0, checked once here on the host; a node without an entry has omega = 1).  None leaves
         the unweighted path untouched.
@@ -83,6 +95,16 @@ class NodeBatch:
         V = plan.V
         if V < 1:
             raise ValueError("rank owns no graph nodes")
+        # bound constraints: checked on the host before any device work
+        self.bounds = check_bounds(bounds, geom.N)
+        kappa = check_bound_weight(bound_weight, self.bounds)
+        if self.bounds is not None:
+            if fusion != "midpoint":
+                raise ValueError("bounds need fusion='midpoint' (the constraint slot has one dual)")
+            if derive_z:
+                raise ValueError("bounds need stored z: the constraint variable w is a stored z row")
+            if Wi_list is None:
+                raise ValueError("bounds need Wi_list: q_c,i = bound_weight * Wi_list[i]")
         wts = node_ray_weights(ray_weights, plan.local_nodes, m)
         if wts is not None and hasattr(geom, "create_ctx"):
             raise ValueError(CSR_WEIGHTS_MSG)
@@ -105,6 +127,8 @@ class NodeBatch:
             self.phantom = _as_f64_tensor(phantom, n, dev)
         # precision vectors q_ij, deduplicated into slots
         E = len(plan.stored_edges)
+        NB = V if self.bounds is not None else 0  # constraint slots: edge slots E .. E + V - 1
+        self.n_real_edges = E
         keyfn = getattr(Qij_diag_fn, "qslot_key", None)
         slots, qvecs, inc_qslot = {}, [], []
         for k, g in enumerate(plan.local_nodes):
@@ -121,28 +145,47 @@ class NodeBatch:
                     slots[key] = len(qvecs)
                     qvecs.append(vec)
                 inc_qslot.append(slots[key])
-        self.q = torch.stack(qvecs) if qvecs else torch.zeros((1, n), dtype=torch.float64, device=dev)
-        self.n_qslots = len(qvecs)
+        self.n_qslots = len(qvecs)  # the real incidences' slots; q_c,k follows in slot n_qslots + k
         self.inc_qslot_host = list(inc_qslot)
+        if NB:
+            qvecs = qvecs + [kappa * _as_f64_tensor(Wi_list[g], n, dev) for g in plan.local_nodes]
+        self.q = torch.stack(qvecs) if qvecs else torch.zeros((1, n), dtype=torch.float64, device=dev)
         ii = lambda a: torch.tensor(a if len(a) else [0], dtype=torch.int32, device=dev)  # noqa: E731
-        self.inc_off = ii(plan.inc_off)
-        self.inc_edge = ii(plan.inc_edge)
-        self.inc_sign = ii(plan.inc_sign)
-        self.inc_qslot = ii(inc_qslot)
-        self.edge_a = ii(plan.edge_a_row)
-        self.edge_b = ii(plan.edge_b_row)
-        self.y = torch.zeros((max(E, 1), n), dtype=torch.float64, device=dev)
+        if NB:
+            # node k's incidences: the plan's, then the constraint's (so c = sum q v adds it last)
+            off, edge, sign, qslot = [0], [], [], []
+            for k in range(V):
+                lo_, hi_ = plan.inc_off[k], plan.inc_off[k + 1]
+                edge += list(plan.inc_edge[lo_:hi_]) + [E + k]
+                sign += list(plan.inc_sign[lo_:hi_]) + [1]
+                qslot += inc_qslot[lo_:hi_] + [self.n_qslots + k]
+                off.append(len(edge))
+            self.inc_off, self.inc_edge, self.inc_sign, self.inc_qslot = ii(off), ii(edge), ii(sign), ii(qslot)
+            self.edge_a = ii(list(plan.edge_a_row) + list(range(V)))
+            self.edge_b = ii(list(plan.edge_b_row) + list(range(V)))
+        else:
+            self.inc_off = ii(plan.inc_off)
+            self.inc_edge = ii(plan.inc_edge)
+            self.inc_sign = ii(plan.inc_sign)
+            self.inc_qslot = ii(inc_qslot)
+            self.edge_a = ii(plan.edge_a_row)
+            self.edge_b = ii(plan.edge_b_row)
+        ES = E + NB  # edge slots the batch is bound with
+        self.y = torch.zeros((max(ES, 1), n), dtype=torch.float64, device=dev)
         # weighted edge fusion: both endpoint duals + W of every x_ext row
         if fusion not in ("midpoint", "weighted"):
             raise ValueError("fusion must be 'midpoint' or 'weighted'")
         if derive_z is None:
             hbm = int(torch.cuda.get_device_properties(dev).total_memory)
-            derive_z = not z_is_stored([E], n, hbm, fusion)
+            derive_z = not z_is_stored([ES], n, hbm, fusion)
+            if derive_z and NB:
+                raise ValueError("bounds need stored z, and this batch's edge state does not fit the stored-z "
+                                 "rule (plan.z_is_stored)")
         if derive_z and fusion != "midpoint":
             raise ValueError("derived z needs midpoint fusion")
         self.derive_z = bool(derive_z)
         # derived: x_ext at the last consensus (x = 0 before the first: z = 0); stored: z per edge
-        self.z = None if self.derive_z else torch.zeros((max(E, 1), n), dtype=torch.float64, device=dev)
+        self.z = None if self.derive_z else torch.zeros((max(ES, 1), n), dtype=torch.float64, device=dev)
         self.x_prev = torch.zeros((plan.n_xext, n), dtype=torch.float64, device=dev) if self.derive_z else None
         self.fusion = fusion
         self.y_b = None
@@ -155,16 +198,17 @@ class NodeBatch:
                                   for g in plan.local_nodes + plan.halo_nodes])
         # D_i = sum_j q_ij  (constant across iterations; setup)
         self.dsum = torch.zeros((V, n), dtype=torch.float64, device=dev)
-        for k in range(V):
-            for q in range(plan.inc_off[k], plan.inc_off[k + 1]):
-                self.dsum[k] += self.q[inc_qslot[q]]
+        self._sum_precisions()
         self.node_stats = torch.zeros((V, _lib.NODE_STATS), dtype=torch.float64, device=dev)
-        self.edge_stats = torch.zeros((max(E, 1), _lib.EDGE_STATS), dtype=torch.float64, device=dev)
+        self.edge_stats = torch.zeros((max(ES, 1), _lib.EDGE_STATS), dtype=torch.float64, device=dev)
+        # the projection's scratch and its per-node sums (|x - w|^2, |w - w_old|^2, |x - clip(x)|^2)
+        self.projector = BoundProjector(self.bounds, n, dev, V) if NB else None
+        self.bound_stats = self.projector.sums if NB else None  # (V, BOUND_STATS), written by the kernel
         self.params = dict(rho=float(rho), lam=float(lam), mu=float(mu), tv_iters=int(tv_iters),
                            cg_iters=int(cg_iters), tv_kind=tv_kind)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
         self.cb = _lib.Batch(
-            V, plan.n_xext, E, int(tv_iters), int(cg_iters),
+            V, plan.n_xext, ES, int(tv_iters), int(cg_iters),
             _lib.ADMM_TV_ANISO if tv_kind == "aniso" else _lib.ADMM_TV_ISO,
             float(rho), float(lam), float(mu),
             p(self.x_ext), p(self.d), p(self.e), p(self.atb), p(self.dsum), p(self.b), p(self.phantom),
@@ -181,6 +225,16 @@ class NodeBatch:
         self._apply_ray_weights()
         _lib.check(self.lib.admm_batch_atb(self.ctx.h, p(self.atb), C.c_void_p(self._s())),
                    "admm_batch_atb")
+
+    def _sum_precisions(self) -> None:
+        """dsum[k] = D_k = sum_j q_kj in incidence order, then q_c,k when the batch has bounds."""
+        plan = self.plan
+        self.dsum.zero_()
+        for k in range(plan.V):
+            for s in range(plan.inc_off[k], plan.inc_off[k + 1]):
+                self.dsum[k] += self.q[self.inc_qslot_host[s]]
+            if self.bounds is not None:
+                self.dsum[k] += self.q[self.n_qslots + k]
 
     def _weights_tensor(self, wts):
         """{g: (m,)} host weights -> the batch's [V][m] device tensor (1 where a node has none)."""
@@ -218,17 +272,15 @@ class NodeBatch:
 
     def set_precisions(self, qs) -> None:
         """New q_ij for a batch bound with one q slot per incidence (in incidence order): the
-        slots are rewritten, D = sum_j q_ij is recomputed as at construction (same order) and the
+        slots are rewritten (q_c of a batch with bounds is not one of them and stays), D = sum_j q_ij
+        (+ q_c) is recomputed as at construction (same order) and the
         batch re-bound (its interleaved D samples and recorded sequences are bind-time data).
         Used by the block_5 drop-in's batch cache."""
         if len(qs) != len(self.inc_qslot_host) or sorted(self.inc_qslot_host) != list(range(len(qs))):
             raise ValueError("set_precisions needs one q slot per incidence")
         for s, q in enumerate(qs):
             self.q[self.inc_qslot_host[s]].copy_(_as_f64_tensor(q, self.geom.n, self.dev))
-        self.dsum.zero_()
-        for k in range(self.V):
-            for s in range(self.plan.inc_off[k], self.plan.inc_off[k + 1]):
-                self.dsum[k] += self.q[self.inc_qslot_host[s]]
+        self._sum_precisions()
         torch.cuda.synchronize(self.dev)
         _lib.check(self.lib.admm_batch_bind(self.ctx.h, C.byref(self.cb)), "admm_batch_bind")
         self._apply_ray_weights()
@@ -254,6 +306,9 @@ class NodeBatch:
         if self.z is None:
             return
         x, w = self.x_ext, self.w
+        if self.bounds is not None:  # constraint slots: w = clip(x), f = 0 (y is zero already)
+            E = self.n_real_edges
+            self.z[E:E + self.V] = self.projector.clip(self.x_local)
         for k in range(len(self.plan.stored_edges)):  # one edge at a time: no [E][n] temporaries
             a, b = self.plan.edge_a_row[k], self.plan.edge_b_row[k]
             if self.fusion == "weighted":
@@ -324,8 +379,26 @@ class NodeBatch:
             t.index_copy_(0, idx, s)
 
     def consensus(self) -> None:
-        if self.plan.stored_edges:
+        if self.bounds is not None:  # the real edges only, then the projection of the constraint slots
+            self.consensus_range(0, self.n_real_edges, self.plan.n_xext)
+            self.bound_project()
+        elif self.plan.stored_edges:
             _lib.check(self.lib.admm_consensus(self.ctx.h, C.c_void_p(self._s())), "admm_consensus")
+
+    @property
+    def w_bound(self) -> torch.Tensor:
+        """w_k of every local node (rows E .. E + V - 1 of z): inside the box exactly."""
+        return self.z[self.n_real_edges:self.n_real_edges + self.V]
+
+    @property
+    def f_bound(self) -> torch.Tensor:
+        """The constraint's scaled dual f_k of every local node (rows E .. E + V - 1 of y)."""
+        return self.y[self.n_real_edges:self.n_real_edges + self.V]
+
+    def bound_project(self) -> None:
+        """w' = clip(x + f), f' = f + x - w' of every local node (admm_bound_project on the current
+        stream; needs no halo row) and ``bound_stats`` <- its three sums per node."""
+        self.projector.run(self.x_local, self.w_bound, self.f_bound, self._s())
 
     def consensus_range(self, e0: int, e1: int, rows: int) -> None:
         """Edge updates of stored slots [e0, e1) only, whose endpoints lie in x_ext rows [0, rows)

@@ -20,6 +20,16 @@ as block_5_node_problem's ``max_iters`` does):
   :58 (+ .png), only for chunked solves, as in the reference (:137-146);
 * ``scs_eps`` / ``scs_use_indirect`` / ``scs_alpha`` / ``scs_acceleration`` /
   ``scs_lookback`` / ``scs_scale``: SCS-only, accepted and ignored.
+
+Beyond the reference's surface:
+
+* ``bounds``    None (default) or (lo, hi): the box lo <= x_i <= hi on every node's image; each is
+                None, a scalar or an (N, N) / (n,) array shared by all nodes (a support mask is
+                hi = 0 outside the support).  Adds the history keys bound_primal, bound_dual,
+                bound_violation, bound_pri_per_node, bound_violation_per_node; needs
+                fusion="midpoint" and stored z (admm_hip/admm.py, admm_hip/bounds.py)
+* ``bound_weight``  kappa > 0 of the constraint's weight q_c,i = kappa * Wi_list[i] (default 1)
+* ``return_feasible``  True: return the constraint copies w_i, inside the box exactly, not x_i
 """
 from __future__ import annotations
 
@@ -45,7 +55,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_acceleration=1, scs_lookback=10, scs_scale=1e-1,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
-                       phantom_true=None, write_params=True, ray_weights=None):
+                       phantom_true=None, write_params=True, bounds=None, bound_weight=None,
+                       return_feasible=False, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
     cg = int(cg_iters)
     total = int(tv_iters) if tv_iters is not None else _rounds(scs_total_iters, cg)
@@ -59,7 +70,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        cg_iters=cg, tv_kind=tv_kind, group=group, write_params=write_params,
                        inner_chunks=chunks,
                        chunk_snapshot_dir=scs_snapshot_dir if chunks is not None else None,
-                       chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights)
+                       chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights, bounds=bounds,
+                       bound_weight=bound_weight, return_feasible=return_feasible)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

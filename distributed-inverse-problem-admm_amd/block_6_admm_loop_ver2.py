@@ -31,6 +31,14 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 (angles, det) / (m,) array for every node, or one entry (array or None) per node;
                 finite and >= 0, 0 masks a ray (geometry operators only)
 
+* ``bounds``    None (default) or (lo, hi): the box lo <= x_i <= hi on every node's image; each is
+                None, a scalar or an (N, N) / (n,) array shared by all nodes (a support mask is
+                hi = 0 outside the support).  Adds the history keys bound_primal, bound_dual,
+                bound_violation, bound_pri_per_node, bound_violation_per_node; needs
+                fusion="midpoint" and stored z (admm_hip/admm.py, admm_hip/bounds.py)
+* ``bound_weight``  kappa > 0 of the constraint's weight q_c,i = kappa * Wi_list[i] (default 1)
+* ``return_feasible``  True: return the constraint copies w_i, inside the box exactly, not x_i
+
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
 from __future__ import annotations
@@ -47,7 +55,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
                        max_inner_updates=10, x_init=None, metrics=None, data_range=None,
-                       metrics_mask=None, ray_weights=None):
+                       metrics_mask=None, bounds=None, bound_weight=None, return_feasible=False,
+                       ray_weights=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
     del max_inner_iters  # accepted but unused, as in the reference (_ver2:17)
     return run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=lam_tv, rho=rho,
@@ -57,4 +66,5 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     tv_iters=tv_iters, cg_iters=cg_iters, tv_kind=tv_kind, group=group,
                     write_params=write_params, fusion=fusion, inner_tol=inner_tol,
                     max_inner_updates=max_inner_updates, x_init=x_init, metrics=metrics,
-                    data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights)
+                    data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights,
+                    bounds=bounds, bound_weight=bound_weight, return_feasible=return_feasible)

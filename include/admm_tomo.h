@@ -71,7 +71,9 @@ extern "C" {
                                    * with ray weights: sum_r omega_r (A x - b)_r^2 */
 #define ADMM_NODE_STAT_G2 1       /* ||g||^2 stationarity    (block_6_admm_loop_ver2.py:145-149) */
 #define ADMM_NODE_STAT_TV 2       /* TV(x)                   (block_4_tv_helpers.py:5-14) */
-#define ADMM_NODE_STAT_QUAD 3     /* sum_j rho/2 ||x-v_ij||^2_Q (block_5_node_problem.py:26-29) */
+#define ADMM_NODE_STAT_QUAD 3     /* sum_j rho/2 ||x-v_ij||^2_Q (block_5_node_problem.py:26-29); a batch
+                                   * bound with a bound-constraint slot per node (admm_bound_project)
+                                   * counts that incidence's term too: it is part of the subproblem */
 #define ADMM_NODE_STAT_IMG 4      /* ||x - phantom||^2       (block_6_admm_loop_ver2.py:199-204) */
 #define ADMM_NODE_STAT_SBRES2 5   /* ||A^T(Ax-b) + rho(D x - c) + mu K^T e||^2: stationarity of eq.(1)
                                      with the split-Bregman dual p = mu e / lam (ABI 3) */
@@ -333,6 +335,33 @@ int admm_image_metrics(const double* img, long long img_stride, const double* re
                        int N, int nimg, double c1, double c2, double* work, double* out, void* stream);
 /* *n_doubles = the doubles of `work` admm_image_metrics needs for this N and nimg.  No device work. */
 int admm_image_metrics_work(int N, int nimg, long long* n_doubles);
+
+/* --- bound constraints lo <= x <= hi on the images --- */
+
+/* The projection step of the splitting x_i = w_i, w_i in [lo, hi], with the scaled dual f_i.  For
+ * image v < nimg and pixel p < n, with x_v = x + v * x_stride, w_v = w + v * wf_stride, f_v = f + v *
+ * wf_stride (doubles; both strides >= n):
+ *   l = lo_map ? max(lo, lo_map[p]) : lo,   h = hi_map ? min(hi, hi_map[p]) : hi
+ *   t = x_v[p] + f_v[p],   w' = t < l ? l : (t > h ? h : t),   f' = t - w'
+ *   out[v] = { sum_p (x - w')^2,  sum_p (w' - w_old)^2,  sum_p (x - P(x))^2 },  P(x) the same clip of x
+ * w_v and f_v are updated in place; out is [nimg][3].  Comparisons, not fmin / fmax: t = -0 with l = 0
+ * stays -0, a tie returns the bound's own bits, and lo = -inf / hi = +inf switch a side off (then w' = t
+ * and f' = +0 exactly).  lo_map / hi_map: one [n] map each shared by every image, or NULL; lo <= hi and
+ * neither NaN (the maps are the caller's to check: admm_hip/bounds.py does).  The x-update reads w as
+ * one more stored z row and f as its y row (incidence sign +1), so the constraint costs the hot kernels
+ * one incidence per node and this call per iteration; with the slot bound, ADMM_NODE_STAT_QUAD includes
+ * its term rho/2 ||x - (w - f)||^2_{q_c}.  Layout of k_consensus<false>: 1024 pixels per block, grid
+ * ceil(n / 1024) x nimg, 8-byte accesses (rows of an odd n need no alignment), 40 B per pixel-image.
+ * No atomics: per-block partial sums in fixed slots of `work` (admm_bound_project_work doubles,
+ * caller-owned), then one fixed-order sum per image, so an image's w, f and three sums depend neither
+ * on nimg, nor on its place in the batch, nor on a stride.  All device pointers float64; nothing is
+ * allocated; context-free like admm_image_metrics; 1 <= nimg <= 65535.  Asynchronous on `stream`
+ * (current device).  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_bound_project(const double* x, long long x_stride, double* w, double* f, long long wf_stride,
+                       const double* lo_map, const double* hi_map, double lo, double hi, long long n,
+                       int nimg, double* work, double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_bound_project needs for this n and nimg.  No device work. */
+int admm_bound_project_work(long long n, int nimg, long long* n_doubles);
 
 #ifdef __cplusplus
 }
