@@ -132,6 +132,13 @@ SYMBOLS = {
     "admm_bound_project": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                            C.c_double, C.c_double, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "admm_bound_project_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_consensus_relaxed": [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                               C.c_void_p],
+    "admm_consensus_relaxed_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_bound_project_relaxed": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                   C.c_void_p, C.c_double, C.c_double, C.c_longlong, C.c_int, C.c_double, C.c_void_p,
+                                   C.c_void_p, C.c_void_p],
 }
 
 _lock = threading.Lock()

@@ -46,6 +46,7 @@ from .groups import RankGroups
 from .solver import node_ray_weights
 from ._lib import NODE_STATS as _NODE_STATS
 from .matrix import MatrixOperator, as_operators
+from .relax import check_relaxation, check_relaxed_run
 from .metrics import check_data_range, check_metrics, check_side, _check_mask_shape
 
 HISTORY_KEYS = (
@@ -93,8 +94,22 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
              pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
-             metrics_mask=None, bounds=None, bound_weight=None, return_feasible=False, ray_weights=None):
-    """``bounds``: None or (lo, hi): the box lo <= x_i <= hi on every node's image; each of lo, hi is
+             metrics_mask=None, relaxation=None, bounds=None, bound_weight=None, return_feasible=False,
+             ray_weights=None):
+    """``relaxation``: None (default) or alpha in the open interval (0, 2): over-relaxation of the
+    consensus step (Eckstein-Bertsekas; Boyd et al. 3.4.3).  In the z- and y-updates of every edge
+    (and in the projection of a run with ``bounds``) x_i is replaced by alpha x_i + (1 - alpha) z_old
+    (admm_consensus_relaxed / admm_bound_project_relaxed, csrc/relax.hip; either fusion).  The
+    residuals keep the true x_i, so ``primal``, ``dual``, the per-node arrays and the stop test keep
+    their definitions, and the run reaches the same fixed point.  Recommended: 1.5 - 1.8 (with the
+    fixed-count x-update 1.6 needs about 0.63 x, 1.8 about 0.56 x the iterations of alpha = 1 to a
+    given residual; values near 2 oscillate with the inexact inner solve); alpha < 1
+    under-relaxes.  A bool, NaN, alpha <= 0 and alpha >= 2 raise ValueError on the host, on every rank
+    alike.  Needs stored z: with edge_state="derived", ADMM_EDGE_STATE=derived, or where the HBM
+    rule picks derived z the run is refused with ValueError (a relaxed z is not the midpoint of the
+    endpoint images).  None and 1.0 change nothing: no launch, no buffer, no history key, bitwise
+    the same results.
+    ``bounds``: None or (lo, hi): the box lo <= x_i <= hi on every node's image; each of lo, hi is
     None (that side off), a scalar, or an (N, N) / (n,) array shared by all nodes (a support mask is
     hi = 0 outside the support); NaN and lo > hi anywhere raise ValueError on the host.  Node i gets
     the splitting x_i = w_i, w_i in the box: one more quadratic term (rho / 2) ||x_i - (w_i - f_i)||^2
@@ -158,6 +173,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     check_bound_run(bounds, fusion, edge_state, os.environ.get("ADMM_EDGE_STATE", ""))
     if return_feasible and bounds is None:
         raise ValueError("return_feasible needs bounds=(lo, hi)")
+    relaxation = check_relaxation(relaxation)
+    check_relaxed_run(relaxation, edge_state, os.environ.get("ADMM_EDGE_STATE", ""))
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through
@@ -183,7 +200,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                     tv_iters, cg_iters, tv_kind, phantom_true, fusion=fusion, Wi_list=Wi_list,
                     keep_x=inner_tol is None, group=group, streams=streams,  # this loop never writes x itself
                     derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state],
-                    ray_weights=ray_weights, bounds=bounds, bound_weight=bound_weight if bounds is not None else None)
+                    ray_weights=ray_weights, bounds=bounds, bound_weight=bound_weight if bounds is not None else None,
+                    relaxation=relaxation)
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
     if start is not None:
@@ -267,7 +285,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         timing["iters"] = iters_done
         timing["V_total"] = V_total
     if write_params and rank == 0:
-        _write_params(snapshot_dir, rho, lam_tv, V_total, mu, tv_iters, cg_iters)
+        _write_params(snapshot_dir, rho, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation)
     if inspect is not None:
         inspect(rg)
     X = rg.images(feasible=bool(return_feasible))
@@ -499,8 +517,8 @@ def _snapshot(snapshot_dir, k, rg, N):
             plt.close()
 
 
-def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters):
-    """_ver2:291-306 admm_internal_params.txt."""
+def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None):
+    """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha)."""
     try:
         log_dir = snapshot_dir if snapshot_dir is not None else os.getcwd()
         os.makedirs(log_dir, exist_ok=True)
@@ -513,6 +531,8 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters):
             f.write("Eps cap = 0.01\n")
             f.write(f"Split-Bregman mu = {mu}\n")
             f.write(f"Inner iterations (tv x cg) = {tv_iters} x {cg_iters}\n")
+            if relaxation is not None:
+                f.write(f"Over-relaxation alpha = {relaxation}\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")
     except Exception as e:  # pragma: no cover
         print(f"[WARN] Could not save internal params: {e}")

@@ -132,10 +132,11 @@ class BoundProjector:
         """clip(x) elementwise with the kernel's comparisons (rows of n pixels)."""
         return torch.where(x < self.l, self.l, torch.where(x > self.h, self.h, x))
 
-    def run(self, x: torch.Tensor, w: torch.Tensor, f: torch.Tensor, stream: int) -> torch.Tensor:
+    def run(self, x: torch.Tensor, w: torch.Tensor, f: torch.Tensor, stream: int, alpha=None) -> torch.Tensor:
         """w, f <- the projection step around the images x (each (nimg, n) float64 with unit pixel
         stride; w and f share one row stride), in place, on ``stream``; returns the (nimg, 3) sums
-        (a view of this object's buffer, rewritten by the next call)."""
+        (a view of this object's buffer, rewritten by the next call).  ``alpha``: the over-relaxed
+        step around alpha x + (1 - alpha) w (admm_bound_project_relaxed; relax.Relaxer)."""
         nimg = x.shape[0]
         if not (1 <= nimg <= self.max_images):
             raise ValueError(f"{nimg} images, the projector holds scratch for {self.max_images}")
@@ -149,7 +150,11 @@ class BoundProjector:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
         xs = x.stride(0) if nimg > 1 else self.n
         ws = w.stride(0) if nimg > 1 else self.n
-        _lib.check(self.lib.admm_bound_project(p(x), xs, p(w), p(f), ws, p(self.lo_map), p(self.hi_map),
-                                               float(self.bounds.lo), float(self.bounds.hi), self.n, nimg,
-                                               p(self.work), p(self.sums), C.c_void_p(stream)), "admm_bound_project")
+        box = (p(x), xs, p(w), p(f), ws, p(self.lo_map), p(self.hi_map), float(self.bounds.lo), float(self.bounds.hi),
+               self.n, nimg)
+        out = (p(self.work), p(self.sums), C.c_void_p(stream))
+        if alpha is None:
+            _lib.check(self.lib.admm_bound_project(*box, *out), "admm_bound_project")
+        else:
+            _lib.check(self.lib.admm_bound_project_relaxed(*box, float(alpha), *out), "admm_bound_project_relaxed")
         return self.sums[:nimg]

@@ -33,6 +33,7 @@ import torch.distributed as dist
 
 from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, z_is_stored
 from .bounds import check_bound_run, check_bound_weight, check_bounds
+from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
 
 
@@ -139,8 +140,11 @@ class RankGroups:
     def __init__(self, A_list, G, V_total: int, world: int, rank: int, sinograms, Qij_diag_fn,
                  rho, lam, mu, tv_iters, cg_iters, tv_kind, phantom, fusion="midpoint", Wi_list=None,
                  keep_x=False, group=None, halo=True, streams=1, derive_z=None,
-                 bounds=None, bound_weight=None, ray_weights=None):
-        """``bounds`` / ``bound_weight``: the box lo <= x <= hi on every image and kappa of
+                 relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
+        """``relaxation``: None or alpha in (0, 2): every batch's edge updates and projection run
+        over-relaxed (NodeBatch; relax.check_relaxation).  It needs stored z: derived z -- forced, or
+        chosen by the HBM rule -- raises ValueError, from run-global facts and so on every rank alike.
+        ``bounds`` / ``bound_weight``: the box lo <= x <= hi on every image and kappa of
         q_c,i = kappa * Wi_list[i] (NodeBatch; bounds.check_bounds).  They need stored z and midpoint
         fusion: derived z -- forced, or chosen by the HBM rule, which counts the V extra rows -- and
         weighted fusion raise ValueError, from run-global facts and so on every rank alike.
@@ -160,6 +164,8 @@ class RankGroups:
         check_bound_weight(bound_weight, self.bounds)
         forced = os.environ.get("ADMM_EDGE_STATE", "")
         check_bound_run(self.bounds, fusion, {None: None, True: "derived", False: "stored"}[derive_z], forced)
+        self.relaxation = check_relaxation(relaxation)
+        check_relaxed_run(self.relaxation, {None: None, True: "derived", False: "stored"}[derive_z], forced)
         if not self.plan.local_nodes:
             raise ValueError(f"rank {rank} owns no graph nodes ({V_total} nodes over {world} ranks)")
         self.world = world
@@ -192,6 +198,9 @@ class RankGroups:
             if derive_z and self.bounds is not None:
                 raise ValueError("bounds need stored z, and this run's edge state (the V constraint rows "
                                  "included) does not fit the stored-z rule (plan.z_is_stored)")
+            if derive_z and self.relaxation is not None:
+                raise ValueError("relaxation needs stored z, and this run's edge state does not fit the stored-z "
+                                 "rule (plan.z_is_stored)")
         self.derive_z = bool(derive_z) if derive_z is not None else False
         devices = {k[0][2] for k in keys}
         if len(devices) > 1:
@@ -208,7 +217,8 @@ class RankGroups:
             self.batches.append(NodeBatch(geom, dtype, gp, sinograms, Qij_diag_fn, rho, lam, mu, tv_iters,
                                           cg_iters, tv_kind, phantom, device, fusion=fusion, Wi_list=Wi_list,
                                           keep_x=keep_x, derive_z=self.derive_z, ray_weights=ray_weights,
-                                          bounds=self.bounds, bound_weight=bound_weight))
+                                          bounds=self.bounds, bound_weight=bound_weight,
+                                          relaxation=self.relaxation))
         self.device = self.batches[0].dev
         if len(self.batches) == 1:
             self.x_rank = self.batches[0].x_ext
@@ -294,7 +304,8 @@ class RankGroups:
         (stored slots [0, n_internal), x_ext rows < V) updated while the halo images are in
         flight: the exchange is issued asynchronously (RCCL on its own stream), those edges run
         on the current stream, then the halo rows land and the remaining edges run.  The same
-        per-edge kernels and statistics as the serial order, bitwise."""
+        per-edge kernels and statistics as the serial order, bitwise (a relaxed run's range calls go
+        to admm_consensus_relaxed)."""
         if not self.overlaps_exchange or os.environ.get("ADMM_EXCHANGE_OVERLAP", "1") == "0":
             self.exchange()
             self.consensus()

@@ -26,6 +26,7 @@ from .bounds import BoundProjector, check_bound_weight, check_bounds
 from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
                        ray_weights_host, _Ctx)
 from .plan import ShardPlan, z_is_stored
+from .relax import Relaxer, check_relaxation
 
 
 def _as_f64_tensor(v, n: int, dev) -> torch.Tensor:
@@ -61,8 +62,13 @@ class NodeBatch:
                  Qij_diag_fn, rho: float, lam: float, mu: float, tv_iters: int = 10,
                  cg_iters: int = 5, tv_kind: str = "iso", phantom=None, device: int = 0,
                  fusion: str = "midpoint", Wi_list=None, keep_x: bool = False, derive_z: bool | None = None,
-                 bounds=None, bound_weight=None, ray_weights=None):
-        """``bounds``: None or (lo, hi) (bounds.check_bounds): the box lo <= x <= hi on every local
+                 relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
+        """``relaxation``: None or alpha in (0, 2) (relax.check_relaxation; 1.0 is None): the edge
+        updates and the constraint's projection run over-relaxed, around alpha x + (1 - alpha) z_old
+        (admm_consensus_relaxed / admm_bound_project_relaxed through ``consensus``, ``consensus_range``
+        and ``bound_project``; either fusion).  Needs stored z.  None: nothing changes, no buffer.
+
+        ``bounds``: None or (lo, hi) (bounds.check_bounds): the box lo <= x <= hi on every local
         image through the splitting x_k = w_k, w_k in the box.  The plan stays as it is; local node k
         gets one more incidence after its real ones -- edge slot E + k (``z[E + k]`` = w_k,
         ``y[E + k]`` = the scaled dual f_k, sign +1, edge_a = edge_b = k) with the q slot
@@ -98,6 +104,9 @@ class NodeBatch:
         # bound constraints: checked on the host before any device work
         self.bounds = check_bounds(bounds, geom.N)
         kappa = check_bound_weight(bound_weight, self.bounds)
+        alpha = check_relaxation(relaxation)
+        if alpha is not None and derive_z:
+            raise ValueError("relaxation needs stored z: a relaxed z is not the midpoint of the endpoint images")
         if self.bounds is not None:
             if fusion != "midpoint":
                 raise ValueError("bounds need fusion='midpoint' (the constraint slot has one dual)")
@@ -181,6 +190,9 @@ class NodeBatch:
             if derive_z and NB:
                 raise ValueError("bounds need stored z, and this batch's edge state does not fit the stored-z "
                                  "rule (plan.z_is_stored)")
+            if derive_z and alpha is not None:
+                raise ValueError("relaxation needs stored z, and this batch's edge state does not fit the "
+                                 "stored-z rule (plan.z_is_stored)")
         if derive_z and fusion != "midpoint":
             raise ValueError("derived z needs midpoint fusion")
         self.derive_z = bool(derive_z)
@@ -204,6 +216,8 @@ class NodeBatch:
         # the projection's scratch and its per-node sums (|x - w|^2, |w - w_old|^2, |x - clip(x)|^2)
         self.projector = BoundProjector(self.bounds, n, dev, V) if NB else None
         self.bound_stats = self.projector.sums if NB else None  # (V, BOUND_STATS), written by the kernel
+        # over-relaxation: alpha and the relaxed edge kernel's scratch (None: the plain updates)
+        self.relaxer = Relaxer(alpha, n, E, dev) if alpha is not None else None
         self.params = dict(rho=float(rho), lam=float(lam), mu=float(mu), tv_iters=int(tv_iters),
                            cg_iters=int(cg_iters), tv_kind=tv_kind)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
@@ -379,7 +393,11 @@ class NodeBatch:
             t.index_copy_(0, idx, s)
 
     def consensus(self) -> None:
-        if self.bounds is not None:  # the real edges only, then the projection of the constraint slots
+        if self.relaxer is not None:  # every real edge (either fusion), then the constraint slots
+            self.relaxer.run_edges(self, 0, self.n_real_edges, self._s())
+            if self.bounds is not None:
+                self.bound_project()
+        elif self.bounds is not None:  # the real edges only, then the projection of the constraint slots
             self.consensus_range(0, self.n_real_edges, self.plan.n_xext)
             self.bound_project()
         elif self.plan.stored_edges:
@@ -397,8 +415,12 @@ class NodeBatch:
 
     def bound_project(self) -> None:
         """w' = clip(x + f), f' = f + x - w' of every local node (admm_bound_project on the current
-        stream; needs no halo row) and ``bound_stats`` <- its three sums per node."""
-        self.projector.run(self.x_local, self.w_bound, self.f_bound, self._s())
+        stream; needs no halo row) and ``bound_stats`` <- its three sums per node.  A relaxed batch
+        projects around alpha x + (1 - alpha) w (admm_bound_project_relaxed)."""
+        if self.relaxer is not None:
+            self.relaxer.run_bounds(self.projector, self.x_local, self.w_bound, self.f_bound, self._s())
+        else:
+            self.projector.run(self.x_local, self.w_bound, self.f_bound, self._s())
 
     def consensus_range(self, e0: int, e1: int, rows: int) -> None:
         """Edge updates of stored slots [e0, e1) only, whose endpoints lie in x_ext rows [0, rows)
@@ -409,6 +431,11 @@ class NodeBatch:
             top = max(max(self.plan.edge_a_row[e0:e1]), max(self.plan.edge_b_row[e0:e1]))
             if top >= rows:
                 raise ValueError(f"edge slots [{e0}, {e1}) reach x_ext row {top} >= rows={rows}")
+            if self.relaxer is not None:
+                if self.fusion != "midpoint":
+                    raise ValueError("consensus_range needs midpoint fusion")
+                self.relaxer.run_edges(self, e0, e1, self._s())
+                return
             _lib.check(self.lib.admm_consensus_range(self.ctx.h, int(e0), int(e1), int(rows), C.c_void_p(self._s())),
                        "admm_consensus_range")
 

@@ -363,6 +363,38 @@ int admm_bound_project(const double* x, long long x_stride, double* w, double* f
 /* *n_doubles = the doubles of `work` admm_bound_project needs for this n and nimg.  No device work. */
 int admm_bound_project_work(long long n, int nimg, long long* n_doubles);
 
+/* --- over-relaxation of the edge and constraint updates --- */
+
+/* The stored-z edge update of admm_consensus with x_i replaced by xh_i = alpha x_i + (1 - alpha) z_old
+ * in the z- and y-updates (Eckstein-Bertsekas over-relaxation), for the edge slots [e0, e1).  Per pixel
+ * of slot e with x_a = x_ext[edge_a[e]], x_b = x_ext[edge_b[e]] and om = 1 - alpha (formed once on the
+ * host), every line one IEEE float64 operation:
+ *   hz = om * z,   xha = alpha * x_a + hz,   xhb = alpha * x_b + hz
+ *   y_b == w == NULL (midpoint):  aa = xha + y,  ab = xhb - y,    z' = (aa + ab) * 0.5
+ *   y_b, w set (weighted):        aa = xha + y,  ab = xhb + y_b,  z' = (W_a aa + W_b ab) / (W_a + W_b),
+ *                                 y_b' = (y_b + xhb) - z'          (W_r = w[r], one row per x_ext row)
+ *   y' = (y + xha) - z'
+ *   edge_stats[e] = { sum (x_a - z')^2, sum (x_b - z')^2, sum (z' - z)^2 }     (the true x_a, x_b)
+ * y, z (and y_b) rows e0 .. e1 - 1 are updated in place and edge_stats rows e0 .. e1 - 1 written; nothing
+ * else is.  x_ext is [n_rows][n]; an edge with an endpoint row outside [0, n_rows) is left unchanged and
+ * its statistics are NaN.  Layout of k_consensus<false>: 1024 pixels per block, one edge per blockIdx.y,
+ * 8-byte accesses, 48 B per pixel-edge.  No atomics: per-(edge, block) partial sums in fixed slots of
+ * `work` (admm_consensus_relaxed_work doubles for at least e1 edges, caller-owned), then one fixed-order
+ * sum per edge, so an edge's results depend neither on [e0, e1) nor on its neighbours.  0 < alpha < 2,
+ * finite (alpha = 1: the unrelaxed update).  Context-free, allocates nothing, asynchronous on `stream`
+ * (current device).  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_consensus_relaxed(const double* x_ext, long long n, int n_rows, double* y, double* y_b, double* z,
+                           const double* w, const int32_t* edge_a, const int32_t* edge_b, int e0, int e1,
+                           double alpha, double* work, double* edge_stats, void* stream);
+/* *n_doubles = the doubles of `work` admm_consensus_relaxed needs for n pixels and n_edges edge slots
+ * (e1 <= n_edges).  No device work. */
+int admm_consensus_relaxed_work(long long n, int n_edges, long long* n_doubles);
+/* admm_bound_project around the relaxed image: t = (alpha * x + om * w) + f, then w', f' and the three
+ * sums as there (the sums with the true x).  `work`: admm_bound_project_work doubles. */
+int admm_bound_project_relaxed(const double* x, long long x_stride, double* w, double* f, long long wf_stride,
+                               const double* lo_map, const double* hi_map, double lo, double hi, long long n,
+                               int nimg, double alpha, double* work, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
