@@ -99,7 +99,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     """``relaxation``: None (default) or alpha in the open interval (0, 2): over-relaxation of the
     consensus step (Eckstein-Bertsekas; Boyd et al. 3.4.3).  In the z- and y-updates of every edge
     (and in the projection of a run with ``bounds``) x_i is replaced by alpha x_i + (1 - alpha) z_old
-    (admm_consensus_relaxed / admm_bound_project_relaxed, csrc/relax.hip; either fusion).  The
+    (admm_consensus_relaxed, admm_bound_project_relaxed; either fusion).  The
     residuals keep the true x_i, so ``primal``, ``dual``, the per-node arrays and the stop test keep
     their definitions, and the run reaches the same fixed point.  Recommended: 1.5 - 1.8 (with the
     fixed-count x-update 1.6 needs about 0.63 x, 1.8 about 0.56 x the iterations of alpha = 1 to a
@@ -170,11 +170,12 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     metrics = _check_metric_args(metrics, data_range, metrics_mask, phantom_true, N)
     bounds = check_bounds(bounds, N)
     bound_weight = check_bound_weight(bound_weight, bounds)
-    check_bound_run(bounds, fusion, edge_state, os.environ.get("ADMM_EDGE_STATE", ""))
+    forced = os.environ.get("ADMM_EDGE_STATE", "")
+    check_bound_run(bounds, fusion, edge_state, forced)
     if return_feasible and bounds is None:
         raise ValueError("return_feasible needs bounds=(lo, hi)")
     relaxation = check_relaxation(relaxation)
-    check_relaxed_run(relaxation, edge_state, os.environ.get("ADMM_EDGE_STATE", ""))
+    check_relaxed_run(relaxation, edge_state, forced)
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through

@@ -1,6 +1,6 @@
 """Bound constraints lo <= x <= hi on the images (scope row f8).
 
-Host side of ``admm_bound_project`` (csrc/bounds.hip): the argument checks, which need no device
+Host side of ``admm_bound_project`` / ``admm_bound_project_relaxed`` (csrc/bounds.hip): the argument checks, which need no device
 (``check_bounds``, ``check_bound_weight``), and ``BoundProjector``, which owns the kernel's scratch
 and the device copies of the maps and enqueues one projection
 

@@ -31,7 +31,7 @@ import torch
 from .exchange import HaloExchange, assemble_stats_device, assemble_stats_parts, gather_images_parts
 import torch.distributed as dist
 
-from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, z_is_stored
+from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, need_stored_z, z_is_stored
 from .bounds import check_bound_run, check_bound_weight, check_bounds
 from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
@@ -163,9 +163,10 @@ class RankGroups:
         self.bounds = check_bounds(bounds, A_list[0].geom.N) if bounds is not None else None
         check_bound_weight(bound_weight, self.bounds)
         forced = os.environ.get("ADMM_EDGE_STATE", "")
-        check_bound_run(self.bounds, fusion, {None: None, True: "derived", False: "stored"}[derive_z], forced)
+        edge_state = {None: None, True: "derived", False: "stored"}[derive_z]
+        check_bound_run(self.bounds, fusion, edge_state, forced)
         self.relaxation = check_relaxation(relaxation)
-        check_relaxed_run(self.relaxation, {None: None, True: "derived", False: "stored"}[derive_z], forced)
+        check_relaxed_run(self.relaxation, edge_state, forced)
         if not self.plan.local_nodes:
             raise ValueError(f"rank {rank} owns no graph nodes ({V_total} nodes over {world} ranks)")
         self.world = world
@@ -195,12 +196,7 @@ class RankGroups:
         if derive_z is None and fusion == "midpoint":
             derive_z = not z_is_stored(stored_edges_per_rank(A_list, G, V_total, world, streams,
                                                              bound_slots=self.bounds is not None), n0, hbm, fusion)
-            if derive_z and self.bounds is not None:
-                raise ValueError("bounds need stored z, and this run's edge state (the V constraint rows "
-                                 "included) does not fit the stored-z rule (plan.z_is_stored)")
-            if derive_z and self.relaxation is not None:
-                raise ValueError("relaxation needs stored z, and this run's edge state does not fit the stored-z "
-                                 "rule (plan.z_is_stored)")
+            need_stored_z(derive_z, self.bounds is not None, self.relaxation is not None, "run")
         self.derive_z = bool(derive_z) if derive_z is not None else False
         devices = {k[0][2] for k in keys}
         if len(devices) > 1:

@@ -1,6 +1,7 @@
 """Over-relaxation of the edge and constraint updates (scope row f9).
 
-Host side of ``admm_consensus_relaxed`` / ``admm_bound_project_relaxed`` (csrc/relax.hip): the
+Host side of ``admm_consensus_relaxed`` (csrc/relax.hip; the relaxed projection of a bounded run is
+``admm_bound_project_relaxed``, csrc/bounds.hip, reached through bounds.BoundProjector): the
 argument checks, which need no device (``check_relaxation``, ``check_relaxed_run``), and ``Relaxer``,
 which owns the edge kernel's scratch and enqueues the relaxed updates of a NodeBatch
 

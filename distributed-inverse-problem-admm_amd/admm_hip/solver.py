@@ -22,11 +22,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .bounds import BoundProjector, check_bound_weight, check_bounds
+from .bounds import BoundProjector, check_bound_run, check_bound_weight, check_bounds
 from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
                        ray_weights_host, _Ctx)
-from .plan import ShardPlan, z_is_stored
-from .relax import Relaxer, check_relaxation
+from .plan import ShardPlan, need_stored_z, z_is_stored
+from .relax import Relaxer, check_relaxation, check_relaxed_run
 
 
 def _as_f64_tensor(v, n: int, dev) -> torch.Tensor:
@@ -105,15 +105,10 @@ class NodeBatch:
         self.bounds = check_bounds(bounds, geom.N)
         kappa = check_bound_weight(bound_weight, self.bounds)
         alpha = check_relaxation(relaxation)
-        if alpha is not None and derive_z:
-            raise ValueError("relaxation needs stored z: a relaxed z is not the midpoint of the endpoint images")
-        if self.bounds is not None:
-            if fusion != "midpoint":
-                raise ValueError("bounds need fusion='midpoint' (the constraint slot has one dual)")
-            if derive_z:
-                raise ValueError("bounds need stored z: the constraint variable w is a stored z row")
-            if Wi_list is None:
-                raise ValueError("bounds need Wi_list: q_c,i = bound_weight * Wi_list[i]")
+        check_relaxed_run(alpha, "derived" if derive_z else None)
+        check_bound_run(self.bounds, fusion, "derived" if derive_z else None)
+        if self.bounds is not None and Wi_list is None:
+            raise ValueError("bounds need Wi_list: q_c,i = bound_weight * Wi_list[i]")
         wts = node_ray_weights(ray_weights, plan.local_nodes, m)
         if wts is not None and hasattr(geom, "create_ctx"):
             raise ValueError(CSR_WEIGHTS_MSG)
@@ -187,12 +182,7 @@ class NodeBatch:
         if derive_z is None:
             hbm = int(torch.cuda.get_device_properties(dev).total_memory)
             derive_z = not z_is_stored([ES], n, hbm, fusion)
-            if derive_z and NB:
-                raise ValueError("bounds need stored z, and this batch's edge state does not fit the stored-z "
-                                 "rule (plan.z_is_stored)")
-            if derive_z and alpha is not None:
-                raise ValueError("relaxation needs stored z, and this batch's edge state does not fit the "
-                                 "stored-z rule (plan.z_is_stored)")
+            need_stored_z(derive_z, bool(NB), alpha is not None, "batch")
         if derive_z and fusion != "midpoint":
             raise ValueError("derived z needs midpoint fusion")
         self.derive_z = bool(derive_z)

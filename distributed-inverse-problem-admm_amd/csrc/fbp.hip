@@ -12,26 +12,13 @@
 //   Ram-Lak      h[0] = 1/(4 tau^2), h[k] = -1/(pi^2 k^2 tau^2) (k odd), 0 (k even)
 //   Shepp-Logan  h[k] = -2/(pi^2 tau^2 (4 k^2 - 1))
 //   Hann         h[k] = rl[k]/2 + (rl[k-1] + rl[k+1])/4   (window (1 + cos 2 pi f tau)/2)
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
-#include <string>
 
-#include "../../include/admm_tomo.h"
-
-namespace admm_internal {
-int fail(int code, const std::string& msg);
-}
+#include "common.hpp"
 
 namespace {
 
 using admm_internal::fail;
-
-#define FHIPCHK(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) return fail(ADMM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 constexpr int kMaxDet = 4096;  // the library's N limit: row + taps = 2 x 32 KiB of LDS
 constexpr int kThreads = 256;
@@ -122,7 +109,7 @@ int admm_fbp_filter(const void* sino, void* out, int dtype, int n_angles, int n_
   else
     hipLaunchKernelGGL((k_fbp_filter<float>), dim3((unsigned)rows), dim3(kThreads), lds, s, (const float*)sino,
                        (float*)out, n_det, det_spacing, gain, filter);
-  FHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ADMM_OK;
 }
 

@@ -17,26 +17,13 @@
 //              go to the higher node index (numpy's usual outcome on tied rows).
 //   chain    : edges between consecutive entries of a per-pixel permutation (:134-151),
 //              drawn on the host by admm_chain_orders (numpy's PCG64 stream, replayed).
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
-#include <string>
 
-#include "../../include/admm_tomo.h"
-
-namespace admm_internal {
-int fail(int code, const std::string& msg);
-}
+#include "common.hpp"
 
 namespace {
 
 using admm_internal::fail;
-
-#define MHIPCHK(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) return fail(ADMM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 constexpr int kMaxV = ADMM_MASK_MAX_NODES;
 
@@ -231,7 +218,7 @@ int admm_pixel_masks(const double* W, int V, int64_t n, int strategy, int k, int
   else
     hipLaunchKernelGGL((k_pixel_masks<64, 64>), dim3((unsigned)blocks), dim3(64), 0, s, W, V, (long long)n,
                        strategy, k, q_mode, ord, kp);
-  MHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ADMM_OK;
 }
 

@@ -17,37 +17,26 @@
 // k_image_metrics: one block per 16 x 32 image tile and image.  The tile plus its 5-pixel halo of
 // img_v and ref is staged once in LDS as float64; a horizontal pass forms the five row moments of
 // every in-image halo row at the tile's valid centre columns, a vertical pass the window moments
-// and S at the valid centres; the block's two sums go to its own slot of `work`.
-// k_image_metrics_sum: one block per image adds the slots in a fixed order.  No atomics anywhere:
-// every sum is a fixed fma / add chain, so an image's outputs depend on its pixels alone.
-#include <hip/hip_runtime.h>
-
+// and S at the valid centres; the block's two sums (block_sums<2>) go to its own slots of `work`,
+// work[(v * 2 + q) * tiles + tile].  k_row_sums<2>: one block per image adds the slots in a fixed
+// order (both: common.hpp).  No atomics anywhere: every sum is a fixed fma / add chain, so an image's
+// outputs depend on its pixels alone.
 #include <cmath>
 #include <cstdint>
-#include <string>
 
-#include "../../include/admm_tomo.h"
+#include "common.hpp"
 
-namespace admm_internal {
-int fail(int code, const std::string& msg);
-}
+using namespace admm;  // kThreads = 256, block_sums, k_row_sums
 
 namespace {
 
 using admm_internal::fail;
 
-#define MHIPCHK(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) return fail(ADMM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
-
 constexpr int kMinN = 11, kMaxN = 4096;  // one window .. the library's N limit
-constexpr int kMaxImg = 65535;           // gridDim.z
+constexpr int kSums = 2;                 // squared error, SSIM sum
 constexpr int kRad = 5, kWin = 2 * kRad + 1;
 constexpr int kTH = 16, kTW = 32;                        // tile: rows x columns
 constexpr int kHH = kTH + 2 * kRad, kHW = kTW + 2 * kRad;  // tile + halo: 26 x 42
-constexpr int kThreads = 256;
 constexpr int kFields = 5;  // x, y, x^2, y^2, xy
 constexpr int kCG = 4;      // horizontal pass: consecutive columns per thread (one row)
 constexpr int kRG = 2;      // vertical pass: consecutive rows per thread (one column): all 256 threads
@@ -59,22 +48,9 @@ struct Taps {
   double w[kWin];
 };
 
-// fixed-order sum of one value per thread: shuffle tree inside each wave, then the waves ascending
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();  // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < kThreads / 64; ++w) s += red[w];
-  return s;
-}
-
-// LDS: sx, sy 2 x 26 x 43 x 8 = 17 888 B, hm 5 x 26 x 33 x 8 = 34 320 B, red 32 B: 52 240 B, three
-// blocks per CU.  Both passes slide a register window so that every LDS value is loaded once per
-// kCG (kRG) outputs: a horizontal-pass thread owns kCG consecutive columns of one row -- its lanes
+// LDS: sx, sy 2 x 26 x 43 x 8 = 17 888 B, hm 5 x 26 x 33 x 8 = 34 320 B, red 64 B: 52 272 B, three
+// blocks per CU (156 816 of the CU's 163 840 B).  Both passes slide a register window so that every
+// LDS value is loaded once per kCG (kRG) outputs: a horizontal-pass thread owns kCG consecutive columns of one row -- its lanes
 // run along the rows, conflict-free through the odd row strides 43 and 33 -- and a vertical-pass
 // thread kRG consecutive rows of one column, lanes along the columns.  Each output's sum is the
 // same ascending-k fma chain whichever thread forms it.
@@ -85,7 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_image_metrics(const double* __rest
   __shared__ double sx[kHH][kSS];
   __shared__ double sy[kHH][kSS];
   __shared__ double hm[kFields][kHH][kMS];
-  __shared__ double red[kThreads / 64];
+  __shared__ double red[kSums][kThreads / 64];
   const int tid = threadIdx.x;
   const int i0 = (int)blockIdx.y * kTH, j0 = (int)blockIdx.x * kTW;  // the tile's first pixel
   const double* x = img + (size_t)blockIdx.z * (size_t)img_stride;
@@ -166,7 +142,8 @@ __global__ __launch_bounds__(kThreads) void k_image_metrics(const double* __rest
 
   // vertical pass + S at the tile's pixels; the squared error of the same pixels
   // (tile rows r0 .. r0 + kRG - 1 of column c; row r's window is hm rows r .. r + 10)
-  double sse = 0.0, ssum = 0.0;
+  double acc[kSums] = {0.0, 0.0};  // squared error, SSIM sum
+  double &sse = acc[0], &ssum = acc[1];
   if (vthread) {
     const int c = vc, r0 = vr0;
     const int gj = j0 + c;
@@ -209,34 +186,12 @@ __global__ __launch_bounds__(kThreads) void k_image_metrics(const double* __rest
       }
     }
   }
-  sse = block_sum(sse, red);
-  ssum = block_sum(ssum, red);
+  block_sums(acc, red);
   if (tid == 0) {
     const size_t tiles = (size_t)gridDim.x * (size_t)gridDim.y;
-    const size_t slot = (size_t)blockIdx.z * tiles + (size_t)blockIdx.y * (size_t)gridDim.x + (size_t)blockIdx.x;
-    work[2 * slot] = sse;
-    work[2 * slot + 1] = ssum;
-  }
-}
-
-// out[v] = the tile slots of image v summed in a fixed order: thread t adds slots t, t + 256, ...
-// ascending, then the 256 thread sums are added ascending by thread 0.
-__global__ __launch_bounds__(kThreads) void k_image_metrics_sum(const double* __restrict__ work, int tiles,
-                                                                double* __restrict__ out) {
-  __shared__ double part[2][kThreads];
-  const double* w = work + 2 * (size_t)blockIdx.x * (size_t)tiles;
-  double a = 0.0, b = 0.0;
-  for (int t = threadIdx.x; t < tiles; t += kThreads) {
-    a += w[2 * (size_t)t];
-    b += w[2 * (size_t)t + 1];
-  }
-  part[0][threadIdx.x] = a;
-  part[1][threadIdx.x] = b;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = part[threadIdx.x][0];
-    for (int t = 1; t < kThreads; ++t) s += part[threadIdx.x][t];
-    out[2 * (size_t)blockIdx.x + threadIdx.x] = s;
+    const size_t tile = (size_t)blockIdx.y * (size_t)gridDim.x + (size_t)blockIdx.x;
+#pragma unroll
+    for (int q = 0; q < kSums; ++q) work[((size_t)blockIdx.z * kSums + q) * tiles + tile] = acc[q];
   }
 }
 
@@ -245,7 +200,7 @@ inline int tiles_y(int N) { return (N + kTH - 1) / kTH; }
 
 int check_shape(int N, int nimg) {
   if (N < kMinN || N > kMaxN) return fail(ADMM_E_INVALID, "N must be in [11, 4096] (one 11 x 11 window .. the library's limit)");
-  if (nimg < 1 || nimg > kMaxImg) return fail(ADMM_E_INVALID, "nimg must be in [1, 65535]");
+  if (nimg < 1 || nimg > kMaxGridY) return fail(ADMM_E_INVALID, "nimg must be in [1, 65535]");
   return ADMM_OK;
 }
 
@@ -256,7 +211,7 @@ extern "C" {
 int admm_image_metrics_work(int N, int nimg, long long* n_doubles) {
   if (!n_doubles) return fail(ADMM_E_INVALID, "n_doubles is null");
   if (int rc = check_shape(N, nimg)) return rc;
-  *n_doubles = 2ll * (long long)tiles_x(N) * (long long)tiles_y(N) * (long long)nimg;
+  *n_doubles = (long long)kSums * (long long)tiles_x(N) * (long long)tiles_y(N) * (long long)nimg;
   return ADMM_OK;
 }
 
@@ -282,9 +237,10 @@ int admm_image_metrics(const double* img, long long img_stride, const double* re
   const int tx = tiles_x(N), ty = tiles_y(N);
   hipLaunchKernelGGL(k_image_metrics, dim3((unsigned)tx, (unsigned)ty, (unsigned)nimg), dim3(kThreads), 0, s, img,
                      img_stride, ref, mask, N, g, c1, c2, work);
-  MHIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_image_metrics_sum, dim3((unsigned)nimg), dim3(kThreads), 0, s, (const double*)work, tx * ty, out);
-  MHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_row_sums<kSums>, dim3((unsigned)nimg), dim3(kThreads), 0, s, (const double*)work,
+                     (long long)tx * ty, 0, out);
+  HIP_TRY(hipGetLastError());
   return ADMM_OK;
 }
 

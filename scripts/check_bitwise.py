@@ -1,6 +1,8 @@
 """Run one small ADMM solve (64^2 or CHECK_N^2, ring of 5 or CHECK_V nodes, 3 iterations, float32 samples) with
-the library ADMM_TOMO_LIB points to and save x / histories; with --compare A.npz B.npz report
-whether two runs are bitwise equal (A/B of code paths that must not change results)."""
+the library ADMM_TOMO_LIB points to and save x and every numeric history key; with --compare A.npz
+B.npz report whether two runs are bitwise equal (A/B of code paths that must not change results).
+Optional paths, each switched on from the environment: CHECK_BOUNDS=1 (bounds=(0, 1)),
+CHECK_RELAX=1.6 (relaxation), CHECK_FUSION=weighted, CHECK_METRICS=1 (metrics=("psnr", "ssim"))."""
 import os
 import sys
 
@@ -10,9 +12,12 @@ import numpy as np  # noqa: E402
 
 if sys.argv[1] == "--compare":
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
-    same = all(np.array_equal(a[k], b[k]) for k in a.files)
-    diff = max(float(np.max(np.abs(a[k] - b[k]))) for k in a.files)
-    print(f"bitwise equal: {same}  (max |diff| {diff:.3e})")
+    same = sorted(a.files) == sorted(b.files) and all(
+        a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes() for k in a.files)
+    diff = max([float(np.nanmax(np.abs(a[k] - b[k]))) for k in a.files
+                if k in b.files and a[k].shape == b[k].shape and a[k].size and not np.all(np.isnan(a[k] - b[k]))],
+               default=0.0)
+    print(f"bitwise equal: {same}  ({len(a.files)} arrays, max |diff| {diff:.3e})")
     sys.exit(0 if same else 1)
 
 import networkx as nx  # noqa: E402
@@ -29,9 +34,25 @@ ops = make_operators(N, V, angles_total=240, device=0)
 ph = shepp_logan(N)
 sinos = make_sinograms(ops, ph, 0.005)
 Wi, Q = make_precisions(ops)
+kw = {}
+if os.environ.get("CHECK_BOUNDS"):
+    kw["bounds"] = (0.0, 1.0)
+if os.environ.get("CHECK_RELAX"):
+    kw["relaxation"] = float(os.environ["CHECK_RELAX"])
+if os.environ.get("CHECK_FUSION"):
+    kw["fusion"] = os.environ["CHECK_FUSION"]
+if os.environ.get("CHECK_METRICS"):
+    kw["metrics"] = ("psnr", "ssim")
 x, h = decentralized_admm(ops, sinos, nx.cycle_graph(V), Wi, Q, N, lam_tv=0.02, rho=2.0, max_iters=3,
-                          eps_pri=0.0, eps_dual=0.0, verbose=False, phantom_true=ph.numpy(), write_params=False)
-np.savez(sys.argv[1], x=np.stack(x), primal=np.array(h["primal"]), dual=np.array(h["dual"]),
-         g=np.stack(h["g_norm_history"]), mse=np.array(h["mse_sino_total"]))
+                          eps_pri=0.0, eps_dual=0.0, verbose=False, phantom_true=ph.numpy(), write_params=False, **kw)
+out = {"x": np.stack(x)}
+for k, v in h.items():  # every history key that holds numbers (one entry per iteration)
+    try:
+        arr = np.asarray(v)
+    except ValueError:
+        continue
+    if arr.size and arr.dtype.kind in "fiub":
+        out["h_" + k] = arr
+np.savez(sys.argv[1], **out)
 torch.cuda.synchronize()
-print("saved", sys.argv[1])
+print("saved", sys.argv[1], sorted(out))

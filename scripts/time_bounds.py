@@ -4,11 +4,11 @@ Default (``--ab``): C3 (512^2, 16-node ring, float32 samples; bench.py's constan
 run_admm in the pipelined mode, alternating ``bounds=None`` and ``bounds=(0, 1)``, five runs each
 after a warm-up of both: ms per iteration of every run, the mean overhead and the unbounded runs'
 own spread.  The bounded run does one more incidence per node in the gather / start / DIAG kernels
-and one admm_bound_project (k_bound_project + k_bound_sum) per iteration.
+and one admm_bound_project (k_bound_project<false> + k_row_sums<3>) per iteration.
 
 ``--one off|on``: one such run and nothing else, for a kernel-stats profile of either form
 (rocprofv3 --kernel-trace --stats -- python scripts/time_bounds.py --one on; scripts/top_kernels.py
-lists k_bound_project next to k_consensus<false>: 40 B against 48 B per pixel-row)."""
+lists k_bound_project<false> next to k_consensus<false>: 40 B against 48 B per pixel-row)."""
 import json
 import sys
 

@@ -3,7 +3,7 @@
 Default (``--ab``): C3 (512^2, 16-node ring, float32 samples; bench.py's constants) through
 run_admm in the pipelined mode, alternating ``relaxation=None`` and ``relaxation=1.6``, five runs each
 after a warm-up of both: ms per iteration of every run, the mean difference and the unrelaxed runs'
-own spread.  The relaxed run enqueues k_consensus_relaxed<false> + k_relax_sum per iteration where the
+own spread.  The relaxed run enqueues k_consensus_relaxed<false> + k_row_sums<3> per iteration where the
 plain one replays the recorded k_consensus<false> + its reduction; both request 48 B per pixel-edge.
 
 ``--one off|on``: one such run and nothing else, for a kernel-stats profile of either form
