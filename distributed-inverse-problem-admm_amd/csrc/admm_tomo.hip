@@ -662,6 +662,15 @@ EdgeIn edge_in(const admm_batch& B) {
   return E;
 }
 
+// k_tv_update of a split-Bregman round: the last round writes d and e; a round after the first
+// reads u, and every round but the last of several leaves u (the five forms an x-update reaches)
+template <typename T, int VB>
+auto tv_kernel(bool last, bool uin, bool uout) {
+  if (last) return uin ? k_tv_update<T, VB, true, true, false> : k_tv_update<T, VB, true, false, false>;
+  if (uin) return k_tv_update<T, VB, false, true, true>;
+  return uout ? k_tv_update<T, VB, false, false, true> : k_tv_update<T, VB, false, false, false>;
+}
+
 // --------------------------------------------------------------------------
 // the x-update sequence for the bound batch (replaces block_6_admm_loop_ver2.py:81-197)
 // --------------------------------------------------------------------------
@@ -682,7 +691,7 @@ int enqueue_update(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 
   double* redH = (double*)C->redH.p;
   const dim3 tg = tile_grid(C, nch, VB);
   const dim3 cgg((N + kTile - 1) / kTile, (N + kCgRows - 1) / kCgRows, nch);
-  const dim3 tvg((N + kTvTile - 1) / kTvTile, (N + TvMap<VB>::TI - 1) / TvMap<VB>::TI, nch);  // k_tv_update
+  const dim3 tvg((N + kTvTile - 1) / kTvTile, (N + EwMap<VB>::TI - 1) / EwMap<VB>::TI, nch);  // k_tv_update
   const int Pb = C->P_back;
 
   // (D as interleaved samples for the CG operator, dsumS, is packed once at bind time)
@@ -767,13 +776,9 @@ int enqueue_update(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 
       RET((launch_back<T, VB, BACK_H>(C, a, V, s)));
       if (bev) HIPCHK(hipEventRecord(bev[1].e, s));
       RET(launch_reduce((double*)C->partH.p, 5 * V, Pb, rk, 1, 1, 0, s));
-      if (kk + 1 < K) {
-        if (F == 2)
-          hipLaunchKernelGGL((k_cg_update<T, VB, true, false>), cgg, dim3(kBlock), 0, s, xcur, r, (const T*)pk, pT,
-                             Hp, rk, N, V, slot[kk + 1]);
-        else
-          hipLaunchKernelGGL((k_cg_update<T, VB, true, true>), cgg, dim3(kBlock), 0, s, xcur, r, (const T*)pk, pT,
-                             Hp, rk, N, V, pk);
+      if (kk + 1 < K) {  // (ring: x is left to the TV update and p_k+1 takes its own slot)
+        const auto cg = (F == 2) ? k_cg_update<T, VB, false> : k_cg_update<T, VB, true>;
+        hipLaunchKernelGGL(cg, cgg, dim3(kBlock), 0, s, xcur, r, pk, pT, Hp, rk, N, V, (F == 2) ? slot[kk + 1] : pk);
         CHECK_LAUNCH();
       }  // the round's last step: applied by the TV update
     }
@@ -793,18 +798,8 @@ int enqueue_update(admm_ctx* C, hipStream_t s, bool reuse = false, int rounds = 
     const double* ein = ecur;  // (not read when uin)
     double* dout = uout ? ((t % 2) ? ub : ua) : (Tt > 1 ? B.d : dnxt);
     double* eout = uout ? nullptr : (Tt > 1 ? B.e : enxt);
-#define TV_LAUNCH(LASTV, FUSEV, UINV, UOUTV)                                                                     \
-  hipLaunchKernelGGL((k_tv_update<T, VB, LASTV, FUSEV, UINV, UOUTV>), tvg, dim3(kTvThreads), 0, s, xcur, din, ein, dout, \
-                     eout, r, pout, poutT, tau, B.mu, B.tv_kind, N, V, xnxt, pr, Hp, redH)
-    if (!last) {
-      if (uin) TV_LAUNCH(false, true, true, true);
-      else if (uout) TV_LAUNCH(false, true, false, true);
-      else TV_LAUNCH(false, true, false, false);
-    } else {
-      if (uin) TV_LAUNCH(true, true, true, false);
-      else TV_LAUNCH(true, true, false, false);
-    }
-#undef TV_LAUNCH
+    hipLaunchKernelGGL((tv_kernel<T, VB>(last, uin, uout)), tvg, dim3(kTvThreads), 0, s, xcur, din, ein, dout, eout, r,
+                       pout, poutT, tau, B.mu, B.tv_kind, N, V, xnxt, pr, Hp, redH);
     CHECK_LAUNCH();
     if (Tt == 1) {  // one round: d, e went to the scratch pair
       std::swap(dcur, dnxt);
@@ -882,27 +877,17 @@ int enqueue_consensus(admm_ctx* C, hipStream_t s) {
   if (B.z == nullptr) {  // derived z (midpoint fusion, ABI 7)
     const dim3 g((npix + kConsPix - 1) / kConsPix);
     double* part = (double*)C->partE.p;
-    switch (cons_rows(B.n_xext)) {
-      case 16:
-        hipLaunchKernelGGL(k_consensus_derived<16>, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a,
-                           B.edge_b, part, npix, B.n_xext, B.n_edges);
-        break;
-      case 64:
-        hipLaunchKernelGGL(k_consensus_derived<64>, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a,
-                           B.edge_b, part, npix, B.n_xext, B.n_edges);
-        break;
-      case 128:
-        hipLaunchKernelGGL(k_consensus_derived<128>, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a,
-                           B.edge_b, part, npix, B.n_xext, B.n_edges);
-        break;
-      default: {
-        hipLaunchKernelGGL(k_consensus_derived_direct, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a,
-                           B.edge_b, part, npix, B.n_edges);
-        CHECK_LAUNCH();
-        const size_t cnt = (size_t)B.n_xext * npix;
-        hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)std::min<size_t>((cnt + kBlock - 1) / kBlock, 16384)),
-                           dim3(kBlock), 0, s, (const double*)B.x_ext, B.x_prev, cnt);
-      }
+    if (const int rows = cons_rows(B.n_xext)) {
+      const auto kern = rows == 16 ? k_consensus_derived<16> : rows == 64 ? k_consensus_derived<64> : k_consensus_derived<128>;
+      hipLaunchKernelGGL(kern, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a, B.edge_b, part, npix, B.n_xext,
+                         B.n_edges);
+    } else {
+      hipLaunchKernelGGL(k_consensus_derived_direct, g, dim3(kBlock), 0, s, B.x_ext, B.x_prev, B.y, B.edge_a,
+                         B.edge_b, part, npix, B.n_edges);
+      CHECK_LAUNCH();
+      const size_t cnt = (size_t)B.n_xext * npix;
+      hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)std::min<size_t>((cnt + kBlock - 1) / kBlock, 16384)),
+                         dim3(kBlock), 0, s, (const double*)B.x_ext, B.x_prev, cnt);
     }
     CHECK_LAUNCH();
     RET(launch_reduce(part, 3 * B.n_edges, C->P_edge, B.edge_stats, 1, 1, 0, s));

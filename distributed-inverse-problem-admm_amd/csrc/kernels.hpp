@@ -2488,31 +2488,58 @@ __global__ __launch_bounds__(kBkThreads) void k_back_mirror_2_gepi(BackArgs<T> A
 // (through a 4 KB LDS tile; every transposed row run is 32 samples = one 128-B
 // line for float), because the forward projector reads the transposed copy for
 // case-A angles.  blockIdx.z = chunk.
+// The map, the LDS tile and the transposed store are written once, for a tile TW columns wide
+// and a block of THREADS threads: (kTile, kBlock) here, (kTvTile, kTvThreads) = (64, 512) in
+// the TV update.  k_start_reuse and k_cg_update (one thread per pixel, all VB nodes) use the
+// tile and the store with their own row count.
 // ===========================================================================
-template <int VB>
+template <int VB, int TW = kTile, int THREADS = kBlock>
 struct EwMap {
-  static constexpr int TI = kTile / VB;  // tile rows
-  static constexpr int RPI = 8 / VB;     // rows per iteration
+  static constexpr int TI = kTile / VB;             // tile rows
+  static constexpr int RPI = THREADS / (TW * VB);   // rows per iteration
   int u, jj, isub;
-  __device__ EwMap() : u(threadIdx.x % VB), jj((threadIdx.x / VB) % kTile), isub(threadIdx.x / (kTile * VB)) {}
+  __device__ EwMap() : u(threadIdx.x % VB), jj((threadIdx.x / VB) % TW), isub(threadIdx.x / (TW * VB)) {}
 };
 
-template <typename T, int VB>
+template <typename T, int VB, int ROWS = kTile / VB, int TW = kTile>
 struct TileT {
-  T t[EwMap<VB>::TI][kTile + 1][VB];
+  T t[ROWS][TW + 1][VB];
 };
 
-// outT (interleaved, chunk base applied by caller): outT[j][i][u] = tile[i - i0][j - j0][u]
-template <typename T, int VB>
-__device__ __forceinline__ void tile_store_T(TileT<T, VB>& tl, T* __restrict__ outT, int N, int i0, int j0) {
-  constexpr int TI = EwMap<VB>::TI;
+// outT (interleaved, chunk base applied by caller): outT[j][i][u] = tile[i - i0][j - j0][u],
+// runs of ROWS x VB samples per column; THREADS: the block's size
+template <typename T, int VB, int ROWS, int TW, int THREADS>
+__device__ __forceinline__ void tile_store_T(TileT<T, VB, ROWS, TW>& tl, T* __restrict__ outT, int N, int i0,
+                                             int j0) {
   __syncthreads();
-  const int u = threadIdx.x % VB, r = (threadIdx.x / VB) % TI, c0 = threadIdx.x / (VB * TI);
-  for (int c = c0; c < kTile; c += kBlock / (VB * TI)) {
+  const int u = threadIdx.x % VB, r = (threadIdx.x / VB) % ROWS, c0 = threadIdx.x / (VB * ROWS);
+  for (int c = c0; c < TW; c += THREADS / (VB * ROWS)) {
     const int jj = j0 + c, ii = i0 + r;
     if (jj < N && ii < N) outT[((size_t)jj * N + ii) * VB + u] = tl.t[r][c][u];
   }
 }
+
+// Linear slot q of a (ROWS, TW + 2) staging region (a tile's rows with a one-pixel halo column
+// on each side) -> row rr and column cc: the TW tile columns cc = 1 .. TW of every row first
+// (aligned float64 runs per node: no lane group straddles a cache line), the two halo columns
+// cc = 0 and TW + 1 after them
+template <int ROWS, int TW>
+__device__ __forceinline__ void halo_slot(int q, int& rr, int& cc) {
+  if (q < ROWS * TW) {
+    rr = q / TW;
+    cc = 1 + q % TW;
+  } else {
+    const int h = q - ROWS * TW;
+    rr = h >> 1;
+    cc = (h & 1) ? TW + 1 : 0;
+  }
+}
+
+// The CG step length from the five sums S = (p.Hp, r.Hp, Hp.Hp, r.r, r.p) of a BACK_H launch:
+// alpha = r.p / p.Hp (exact line search), 0 where p.Hp = 0
+__device__ __forceinline__ double cg_alpha(const double* S) { return (S[0] != 0.0) ? S[4] / S[0] : 0.0; }
+
+constexpr int kCgRows = kBlock / kTile;  // the pixel-per-thread kernels' block: 8 rows x 32 columns
 
 // CG start from the previous x-update's diagnostics (batch flag ADMM_BATCH_KEEP_X: x_ext's
 // local rows were last written by admm_node_update).  The previous DIAG left
@@ -2524,9 +2551,8 @@ __device__ __forceinline__ void tile_store_T(TileT<T, VB>& tl, T* __restrict__ o
 // are (T) x read straight from x), p also written transposed.  One thread per pixel, all
 // VB nodes of the chunk; a block is kTile x kCgRows pixels (the CG update's grid).
 // The block stages (T) x of its tile plus a one-pixel halo per node in LDS once
-// (the tile's 32 aligned columns of every row first, then the two halo columns) and the
-// stencil reads it there -- 2 float64 loads per thread and node instead of 5, the same casts
-// in the same order.
+// (slot order: halo_slot) and the stencil reads it there -- 2 float64 loads per thread and node
+// instead of 5, the same casts in the same order.
 template <typename T, int VB>
 __global__ __launch_bounds__(kBlock) void k_start_reuse(
     const T* __restrict__ ats, const double* __restrict__ x, EdgeIn E, const double* __restrict__ q,
@@ -2534,8 +2560,8 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
     const int* __restrict__ inc_sign, const double* __restrict__ atb, double* __restrict__ cvec,
     const double* __restrict__ dsum, const double* __restrict__ dvar, const double* __restrict__ evar,
     double* __restrict__ r, T* __restrict__ p, T* __restrict__ pT, double rho, double mu, int N, int V) {
-  constexpr int ROWS = kBlock / kTile;
-  __shared__ T tl[ROWS][kTile + 1][VB];
+  constexpr int ROWS = kCgRows;
+  __shared__ TileT<T, VB, ROWS> tl;
   const int chunk = blockIdx.z, v0 = chunk * VB, nv = min(VB, V - v0);
   const int npix = N * N;
   const size_t sbase = (size_t)chunk * npix * VB;
@@ -2544,7 +2570,7 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
   const int i = i0 + ii, j = j0 + jj;
   __shared__ T xt[VB][ROWS + 2][kTile + 2];  // (T) x over rows i0 - 1 .., columns j0 - 1 ..; 0 off the image
   {
-    constexpr int NIN = (ROWS + 2) * kTile, NEL = (ROWS + 2) * (kTile + 2);
+    constexpr int NEL = (ROWS + 2) * (kTile + 2);
     constexpr int PER = (NEL + kBlock - 1) / kBlock;
     double xl[VB][PER];
 #pragma unroll
@@ -2552,8 +2578,8 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
 #pragma unroll
       for (int e = 0; e < PER; ++e) {
         const int q = (int)threadIdx.x + e * kBlock;
-        const int rr = q < NIN ? q / kTile : (q - NIN) >> 1;
-        const int cc = q < NIN ? 1 + q % kTile : ((q - NIN) & 1) * (kTile + 1);
+        int rr, cc;
+        halo_slot<ROWS + 2, kTile>(q, rr, cc);
         const int row = i0 - 1 + rr, col = j0 - 1 + cc;
         const bool in = q < NEL && u < nv && row >= 0 && row < N && col >= 0 && col < N;
         xl[u][e] = in ? x[(size_t)(v0 + u) * npix + row * N + col] : 0.0;
@@ -2563,8 +2589,8 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
 #pragma unroll
       for (int e = 0; e < PER; ++e) {
         const int q = (int)threadIdx.x + e * kBlock;
-        const int rr = q < NIN ? q / kTile : (q - NIN) >> 1;
-        const int cc = q < NIN ? 1 + q % kTile : ((q - NIN) & 1) * (kTile + 1);
+        int rr, cc;
+        halo_slot<ROWS + 2, kTile>(q, rr, cc);
         if (q < NEL) xt[u][rr][cc] = (T)xl[u][e];
       }
     __syncthreads();
@@ -2598,17 +2624,11 @@ __global__ __launch_bounds__(kBlock) void k_start_reuse(
         r[vo + pix] = rr;
         outv[u] = (T)rr;
       }
-      tl[ii][jj][u] = outv[u];
+      tl.t[ii][jj][u] = outv[u];
     }
     gstore<T, VB>(p + sbase + (size_t)pix * VB, outv);
   }
-  __syncthreads();
-  // transposed copy: pT[j][i][u], runs of ROWS x VB samples per column
-  const int u = threadIdx.x % VB, rr_ = (threadIdx.x / VB) % ROWS, c0 = threadIdx.x / (VB * ROWS);
-  for (int c = c0; c < kTile; c += kBlock / (VB * ROWS)) {
-    const int jc = j0 + c, ic = i0 + rr_;
-    if (jc < N && ic < N) pT[sbase + ((size_t)jc * N + ic) * VB + u] = tl[rr_][c][u];
-  }
+  tile_store_T<T, VB, ROWS, kTile, kBlock>(tl, pT + sbase, N, i0, j0);
 }
 
 // gather (prologue of the x-update, block_6_admm_loop_ver2.py:85-95,137-140):
@@ -2646,7 +2666,7 @@ __global__ __launch_bounds__(kBlock) void k_gather(const double* __restrict__ x,
       tl.t[r][mp.jj][mp.u] = sv;
     }
   }
-  tile_store_T<T, VB>(tl, xsT + sbase, N, i0, j0);
+  tile_store_T<T, VB, EwMap<VB>::TI, kTile, kBlock>(tl, xsT + sbase, N, i0, j0);
 }
 
 template <typename T, int VB>
@@ -2659,7 +2679,7 @@ __global__ __launch_bounds__(kBlock) void k_transpose(const T* __restrict__ in, 
     const int i = i0 + r, j = j0 + mp.jj;
     if (i < N && j < N) tl.t[r][mp.jj][mp.u] = in[sbase + ((size_t)i * N + j) * VB + mp.u];
   }
-  tile_store_T<T, VB>(tl, outT + sbase, N, i0, j0);
+  tile_store_T<T, VB, EwMap<VB>::TI, kTile, kBlock>(tl, outT + sbase, N, i0, j0);
 }
 
 // CG step from the five reductions of the preceding BACK_H launch (oracle/node_solver.py):
@@ -2668,22 +2688,17 @@ __global__ __launch_bounds__(kBlock) void k_transpose(const T* __restrict__ in, 
 // One thread per pixel, all VB nodes of the chunk: the interleaved p / Hp samples are
 // one 32-B vector per lane and every node's float64 x / r is read in 32-pixel (256-B)
 // runs (a node-per-lane mapping splits those into 64-B pieces across 8 arrays 2 MB apart).
-constexpr int kCgRows = kBlock / kTile;  // 8 rows x 32 columns per block
-
-// The CG x steps of a split-Bregman round are applied by the TV update that ends the round
-// (k_tv_update FUSE): all K of them from a ring of the round's directions when K <=
-// kMaxCgRing, else only the round's last one.
-// WRITE_P = false: the last CG step of a split-Bregman round -- the TV update (or the next
-// x-update's start) overwrites p and its transposed copy, so only x and r are written
-// WRITE_X = false (direction ring): x is left alone -- the TV update applies the round's
-// x += alpha_k p_k, k = 0..K-1, in the same order (so bitwise the same x) from the p ring;
-// p_{k+1} then goes to its own slot pout (p_k stays readable for that).
-template <typename T, int VB, bool WRITE_P = true, bool WRITE_X = true>
+// The last CG step of a split-Bregman round has no launch of this kernel: the TV update that
+// ends the round applies it (k_tv_update).
+// WRITE_X = false (direction ring, K <= kMaxCgRing): x is left alone -- the TV update applies
+// the round's x += alpha_k p_k, k = 0..K-1, in the same order (so bitwise the same x) from the
+// p ring; p_{k+1} then goes to its own slot pout (p_k stays readable for that).
+template <typename T, int VB, bool WRITE_X>
 __global__ __launch_bounds__(kBlock) void k_cg_update(double* __restrict__ x, double* __restrict__ r,
                                                       const T* p, T* __restrict__ pT,
                                                       const T* __restrict__ Hp, const double* __restrict__ redH,
                                                       int N, int V, T* pout) {
-  __shared__ T tl[kCgRows][kTile + 1][VB];
+  __shared__ TileT<T, VB, kCgRows> tl;
   __shared__ double ab_s[VB][2];
   const int chunk = blockIdx.z, v0 = chunk * VB;
   const int npix = N * N;
@@ -2693,8 +2708,8 @@ __global__ __launch_bounds__(kBlock) void k_cg_update(double* __restrict__ x, do
     double alpha = 0.0, beta = 0.0;
     if (v < V) {
       const double* S = redH + 5 * v;
-      const double pHp = S[0], rHp = S[1], HH = S[2], rr = S[3], rp = S[4];
-      alpha = (pHp != 0.0) ? rp / pHp : 0.0;
+      const double rHp = S[1], HH = S[2], rr = S[3];
+      alpha = cg_alpha(S);
       double rrn = rr - 2.0 * alpha * rHp + alpha * alpha * HH;
       rrn = fmax(rrn, 0.0);
       beta = (rr != 0.0) ? rrn / rr : 0.0;
@@ -2718,23 +2733,16 @@ __global__ __launch_bounds__(kBlock) void k_cg_update(double* __restrict__ x, do
         const size_t o = (size_t)(v0 + u) * npix + pix;
         const double alpha = ab_s[u][0], beta = ab_s[u][1];
         const double pd = (double)pv[u];
-        if constexpr (WRITE_X) x[o] = fma(alpha, pd, x[o]);  // (explicit fma: k_tv_update<FUSE> repeats it bitwise)
+        if constexpr (WRITE_X) x[o] = fma(alpha, pd, x[o]);  // (explicit fma: k_tv_update repeats it bitwise)
         const double rn = fma(-alpha, (double)hv[u], r[o]);
         r[o] = rn;
         np[u] = (T)(rn + beta * pd);
       }
-      if constexpr (WRITE_P) tl[ii][jj][u] = np[u];
+      tl.t[ii][jj][u] = np[u];
     }
-    if constexpr (WRITE_P) gstore<T, VB>(pout + sbase + (size_t)pix * VB, np);
+    gstore<T, VB>(pout + sbase + (size_t)pix * VB, np);
   }
-  if constexpr (!WRITE_P) return;
-  __syncthreads();
-  // transposed copy: pT[j][i][u], runs of kCgRows x VB samples per column
-  const int u = threadIdx.x % VB, rr_ = (threadIdx.x / VB) % kCgRows, c0 = threadIdx.x / (VB * kCgRows);
-  for (int c = c0; c < kTile; c += kBlock / (VB * kCgRows)) {
-    const int jc = j0 + c, ic = i0 + rr_;
-    if (jc < N && ic < N) pT[sbase + ((size_t)jc * N + ic) * VB + u] = tl[rr_][c][u];
-  }
+  tile_store_T<T, VB, kCgRows, kTile, kBlock>(tl, pT + sbase, N, i0, j0);
 }
 
 // split-Bregman (d, e) update after a CG solve:
@@ -2764,60 +2772,34 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
 }
 
-// FUSE: the round's CG x steps are folded in (all K of them, the CG updates leaving x alone
-// and keeping each direction p_k in a ring slot; K > kMaxCgRing: only the last one).
-// x after those steps is formed once per pixel of the stencil region, from the old x and
-// p_k with the same fmas in the same order, written once to xout (x ping-pongs: neighbour
-// blocks still read the old x), and r gets the last step's update and the TV shift in one
-// pass; the CG restart p = r goes to a slot no one reads here.  Bitwise the same iteration
-// as the separate kernels (scripts/check_bitwise.py).
-// The CG directions whose x steps the fused TV update applies (FUSE): p[k] with alpha_k
-// from the reduction redH + k * 5V, k = 0 .. K-1 (K = 1: only the round's last step).
+// The TV update ends a split-Bregman round and carries the round's CG x steps with it.
+// Direction ring: the round's CG updates leave x alone and keep each direction p_k in a ring
+// slot (PRing: p[k] with alpha_k from the reduction redH + k * 5V, k = 0 .. K-1; with more CG
+// steps than kMaxCgRing slots the CG updates write x themselves and K = 1, the round's last
+// step).  x after those steps is formed once per pixel of the block's stencil region, from the
+// old x and p_k with the CG update's fmas in the same order, and written once to xout (x
+// ping-pongs: neighbour blocks still read the old x); r gets the last step's update and the TV
+// shift in one pass, and the CG restart p = r goes to a slot no one reads here.  Bitwise the
+// same iteration as one kernel per step (scripts/check_bitwise.py).
+// State between rounds (UIN / UOUT): between the rounds of one x-update the split-Bregman state
+// is kept as u = Kx + e_old alone (2 doubles per pixel instead of d and e, 4): the next round
+// recomputes d = shrink(u) and e = u - d -- exactly the values the round that wrote u computed,
+// so the iteration is bitwise the same -- and the traffic of a middle round drops by 4 of its
+// ~34 bytes per node-pixel read+written.  UIN: din holds u (ein unused); UOUT: dout receives u
+// (eout unused).  The x-update's first round reads d, e and its last writes them, so the state
+// between x-updates (and every other kernel) is unchanged.
+// Tile: kTvTile columns x kTile / VB rows of VB nodes, kTvThreads threads (EwMap / TileT at that
+// width), in xcd_remap's order.
 constexpr int kMaxCgRing = 8;
 template <typename T>
 struct PRing {
   const T* p[kMaxCgRing];
   int K;
 };
-// UIN / UOUT: between the rounds of one x-update the split-Bregman state
-// is kept as u = Kx + e_old alone (2 doubles per pixel instead of d and e, 4): the next
-// round recomputes d = shrink(u) and e = u - d -- exactly the values the round that wrote
-// u computed, so the iteration is bitwise the same -- and the traffic of a middle round
-// drops by 4 of its ~34 bytes per node-pixel read+written.  UIN: din holds u (ein unused);
-// UOUT: dout receives u (eout unused).  The x-update's first round reads d, e and its last
-// writes them, so the state between x-updates (and every other kernel) is unchanged.
-// Tile of the TV update: kTvTile columns x kTile / VB rows of VB nodes, kTvThreads threads
-// (ADMM_TV_TW = 64: twice the columns per halo column pair, 512 threads -- fewer partial-line
-// requests per pixel for the same rows; 32: the elementwise kernels' tile, 256 threads)
-#ifndef ADMM_TV_TW
-#define ADMM_TV_TW 64
-#endif
-constexpr int kTvTile = ADMM_TV_TW;
-constexpr int kTvThreads = kTvTile == 64 ? 512 : 256;
+// (64 x 512, not the element-wise 32 x 256: 4 full lines per 2 halo partials a row, 92.0 -> 89.1 us, round 6)
+constexpr int kTvTile = 64, kTvThreads = 512;
 static_assert(kTvTile == 32 || kTvTile == 64, "TV tile width 32 or 64");
-template <int VB>
-struct TvMap {
-  static constexpr int TI = kTile / VB;                       // tile rows
-  static constexpr int RPI = kTvThreads / (kTvTile * VB);     // rows per iteration
-  int u, jj, isub;
-  __device__ TvMap() : u(threadIdx.x % VB), jj((threadIdx.x / VB) % kTvTile), isub(threadIdx.x / (kTvTile * VB)) {}
-};
-template <typename T, int VB>
-struct TvTile {
-  T t[TvMap<VB>::TI][kTvTile + 1][VB];
-};
-// outT[j][i][u] = tile[i - i0][j - j0][u] (as tile_store_T, for the TV tile)
-template <typename T, int VB>
-__device__ __forceinline__ void tv_tile_store_T(TvTile<T, VB>& tl, T* __restrict__ outT, int N, int i0, int j0) {
-  constexpr int TI = TvMap<VB>::TI;
-  __syncthreads();
-  const int u = threadIdx.x % VB, r = (threadIdx.x / VB) % TI, c0 = threadIdx.x / (VB * TI);
-  for (int c = c0; c < kTvTile; c += kTvThreads / (VB * TI)) {
-    const int jj = j0 + c, ii = i0 + r;
-    if (jj < N && ii < N) outT[((size_t)jj * N + ii) * VB + u] = tl.t[r][c][u];
-  }
-}
-template <typename T, int VB, bool LAST, bool FUSE = false, bool UIN = false, bool UOUT = false>
+template <typename T, int VB, bool LAST, bool UIN, bool UOUT>
 __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restrict__ x, const double* __restrict__ din,
                                                       const double* __restrict__ ein, double* __restrict__ dout,
                                                       double* __restrict__ eout, double* __restrict__ r,
@@ -2826,91 +2808,77 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
                                                       PRing<T> pr, const T* __restrict__ Hp,
                                                       const double* __restrict__ redH) {
   static_assert(!(LAST && UOUT), "the last round writes d and e");
-  __shared__ TvTile<T, VB> tl;
-  const TvMap<VB> mp;
+  using Map = EwMap<VB, kTvTile, kTvThreads>;
+  constexpr int TI = Map::TI;
+  __shared__ TileT<T, VB, TI, kTvTile> tl;
+  const Map mp;
   const int chunk = blockIdx.z, v = chunk * VB + mp.u;
   const bool live = v < V;
   const int npix = N * N;
   const size_t sbase = (size_t)chunk * npix * VB;
   const int wg = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  const int i0 = (wg / gridDim.x) * TvMap<VB>::TI, j0 = (wg % gridDim.x) * kTvTile;
-  // FUSE: x after the round's CG steps over the block's stencil region (rows i0-1 .. i0+TI,
-  // columns j0-1 .. j0+kTvTile), formed once per pixel into LDS from the old x and the p ring
-  // (32-B vector loads of each p), x = fma(alpha_k, p_k, x) for k = 0 .. K-1 as the CG
-  // updates did it; the stencil then reads LDS only
-  constexpr int PR = TvMap<VB>::TI + 2, PC = kTvTile + 2;
-  __shared__ double al_s[FUSE ? kMaxCgRing : 1][VB];
-  __shared__ double x_s[FUSE ? VB : 1][FUSE ? PR : 1][FUSE ? PC + 1 : 1];
-  if constexpr (FUSE) {
-    if ((int)threadIdx.x < VB * pr.K) {  // alpha_k per node (as k_cg_update)
-      const int k = threadIdx.x / VB, u = threadIdx.x % VB, vv = chunk * VB + u;
-      double alpha = 0.0;
-      if (vv < V) {
-        const double* S = redH + (size_t)k * 5 * V + 5 * vv;
-        alpha = (S[0] != 0.0) ? S[4] / S[0] : 0.0;
-      }
-      al_s[k][u] = alpha;
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < PR * PC; q += kTvThreads) {
-      // the tile's kTvTile columns first (rows of 256-B-aligned float64 runs per node), the two
-      // halo columns after them: no lane group straddles a cache line
-      int rr, cc;
-      if (q < PR * kTvTile) {
-        rr = q / kTvTile;
-        cc = 1 + q % kTvTile;
-      } else {
-        const int h = q - PR * kTvTile;
-        rr = h >> 1;
-        cc = (h & 1) ? PC - 1 : 0;
-      }
-      const int i = i0 - 1 + rr, j = j0 - 1 + cc;
-      if (i < 0 || j < 0 || i >= N || j >= N) continue;
-      const int o = i * N + j;
-      double xn[VB];
-#pragma unroll
-      for (int u = 0; u < VB; ++u) {
-        const int vq = chunk * VB + u;
-        xn[u] = vq < V ? x[(size_t)vq * npix + o] : 0.0;
-      }
-      // direction k + 1 is loaded before step k's fmas (one load in flight; two: 60.4 us)
-      T pa[VB], pb[VB];
-      gload<T, VB>(pr.p[0] + sbase + (size_t)o * VB, pa);
-      for (int k = 0; k < pr.K; ++k) {
-        if (k + 1 < pr.K) gload<T, VB>(pr.p[k + 1] + sbase + (size_t)o * VB, pb);
-#pragma unroll
-        for (int u = 0; u < VB; ++u) xn[u] = fma(al_s[k][u], (double)pa[u], xn[u]);
-#pragma unroll
-        for (int u = 0; u < VB; ++u) pa[u] = pb[u];
-      }
-#pragma unroll
-      for (int u = 0; u < VB; ++u) x_s[u][rr][cc] = xn[u];
-    }
-    __syncthreads();
+  const int i0 = (wg / gridDim.x) * TI, j0 = (wg % gridDim.x) * kTvTile;
+  // x after the round's CG steps over the block's stencil region (rows i0-1 .. i0+TI, columns
+  // j0-1 .. j0+kTvTile), formed once per pixel into LDS from the old x and the p ring (32-B
+  // vector loads of each p), x = fma(alpha_k, p_k, x) for k = 0 .. K-1 as the CG updates did
+  // it; the stencil then reads LDS only
+  constexpr int PR = TI + 2, PC = kTvTile + 2;
+  __shared__ double al_s[kMaxCgRing][VB];
+  __shared__ double x_s[VB][PR][PC + 1];
+  if ((int)threadIdx.x < VB * pr.K) {  // alpha_k per node (as k_cg_update)
+    const int k = threadIdx.x / VB, u = threadIdx.x % VB, vv = chunk * VB + u;
+    al_s[k][u] = vv < V ? cg_alpha(redH + (size_t)k * 5 * V + 5 * vv) : 0.0;
   }
-  // x of node u of the chunk at (i, j) after the round's CG steps
-  auto xat = [&](int u, const double* xq, int i, int j) -> double {
-    if constexpr (FUSE) return x_s[u][i - i0 + 1][j - j0 + 1];
-    return xq[i * N + j];
+  __syncthreads();
+  for (int q = threadIdx.x; q < PR * PC; q += kTvThreads) {
+    int rr, cc;
+    halo_slot<PR, kTvTile>(q, rr, cc);
+    const int i = i0 - 1 + rr, j = j0 - 1 + cc;
+    if (i < 0 || j < 0 || i >= N || j >= N) continue;
+    const int o = i * N + j;
+    double xn[VB];
+#pragma unroll
+    for (int u = 0; u < VB; ++u) {
+      const int vq = chunk * VB + u;
+      xn[u] = vq < V ? x[(size_t)vq * npix + o] : 0.0;
+    }
+    // direction k + 1 is loaded before step k's fmas (one load in flight; two: 60.4 us)
+    T pa[VB], pb[VB];
+    gload<T, VB>(pr.p[0] + sbase + (size_t)o * VB, pa);
+    for (int k = 0; k < pr.K; ++k) {
+      if (k + 1 < pr.K) gload<T, VB>(pr.p[k + 1] + sbase + (size_t)o * VB, pb);
+#pragma unroll
+      for (int u = 0; u < VB; ++u) xn[u] = fma(al_s[k][u], (double)pa[u], xn[u]);
+#pragma unroll
+      for (int u = 0; u < VB; ++u) pa[u] = pb[u];
+    }
+#pragma unroll
+    for (int u = 0; u < VB; ++u) x_s[u][rr][cc] = xn[u];
+  }
+  __syncthreads();
+  // x of node u of the chunk at (i, j) after the round's CG steps, and its forward differences
+  auto xat = [&](int u, int i, int j) -> double { return x_s[u][i - i0 + 1][j - j0 + 1]; };
+  auto gradx = [&](int u, int i, int j, double& gx, double& gy) {
+    const double c = xat(u, i, j);
+    gx = (i < N - 1) ? xat(u, i + 1, j) - c : 0.0;
+    gy = (j < N - 1) ? xat(u, i, j + 1) - c : 0.0;
   };
-  auto gradx = [&](int u, const double* xq, int i, int j, double& gx, double& gy) {
-    const double c = xat(u, xq, i, j);
-    gx = (i < N - 1) ? xat(u, xq, i + 1, j) - c : 0.0;
-    gy = (j < N - 1) ? xat(u, xq, i, j + 1) - c : 0.0;
-  };
+  // (this round's input d, e -- as stored, or with UIN recomputed from the u the round before left
+  // in din -- is spelled out in both arms below: as a shared lambda it changed the address
+  // arithmetic of every instantiation, and the middle round measured 0.4 % slower)
   const size_t vo = (size_t)(live ? v : 0) * npix;
-  const double* xv = x + vo;
   const double* ev = ein + 2 * vo;
   if constexpr (!LAST) {
     // Phase 1: shrink once per point of the tile plus one halo row (i0-1) and column (j0-1),
     // keeping q = (d' - e') - (d - e) per component in LDS; tile points also store d', e'.
     // Phase 2: K^T q at each tile pixel from LDS (the same four terms, in the same order,
     // that the neighbour re-evaluation used), then r += mu K^T q, p = r.
-    constexpr int TI = TvMap<VB>::TI, HC = kTvTile + 1, HR = TI + 1;
+    constexpr int HC = kTvTile + 1, HR = TI + 1;
     // column-fastest: a wave reads runs of 33 consecutive pixels of one node
     __shared__ double qx_s[HR][VB][HC], qy_s[HR][VB][HC];
     for (int q = threadIdx.x; q < HR * HC * VB; q += kTvThreads) {
-      // (as above: the kTvTile tile columns of every (row, node) first, the halo column after)
+      // (as halo_slot, node inside the row: the kTvTile tile columns of every (row, node) first,
+      // the halo column after)
       int cc, u, rr;
       if (q < HR * VB * kTvTile) {
         cc = 1 + q % kTvTile;
@@ -2927,7 +2895,6 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
       const int vq = chunk * VB + u;
       if (vq >= V || i < 0 || j < 0 || i >= N || j >= N) continue;
       const size_t vqo = (size_t)vq * npix;
-      const double* xq = x + vqo;
       const int o = i * N + j;
       double d0, d1, e0, e1;  // this round's input d and e at (i, j)
       if constexpr (UIN) {
@@ -2942,7 +2909,7 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
         e1 = ein[2 * vqo + npix + o];
       }
       double gx, gy, ndx, ndy;
-      gradx(u, xq, i, j, gx, gy);
+      gradx(u, i, j, gx, gy);
       const double ux = gx + e0, uy = gy + e1;
       shrink2(ux, uy, tau, kind, ndx, ndy);
       const double nex = ux - ndx, ney = uy - ndy;
@@ -2961,7 +2928,7 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
       }
     }
     __syncthreads();
-    for (int rw = mp.isub; rw < TI; rw += TvMap<VB>::RPI) {
+    for (int rw = mp.isub; rw < TI; rw += Map::RPI) {
       const int i = i0 + rw, j = j0 + mp.jj;
       if (i >= N || j >= N) continue;
       const int o = i * N + j;
@@ -2973,10 +2940,8 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
         if (i >= 1) kt += qx_s[rw][mp.u][mp.jj + 1];
         if (j >= 1) kt += qy_s[rw + 1][mp.u][mp.jj];
         double rv = r[vo + o];
-        if constexpr (FUSE) {
-          rv = fma(-al_s[pr.K - 1][mp.u], (double)Hp[sbase + (size_t)o * VB + mp.u], rv);
-          xout[vo + o] = xat(mp.u, xv, i, j);
-        }
+        rv = fma(-al_s[pr.K - 1][mp.u], (double)Hp[sbase + (size_t)o * VB + mp.u], rv);
+        xout[vo + o] = xat(mp.u, i, j);
         const double rn = fma(mu, kt, rv);
         r[vo + o] = rn;
         sv = (T)rn;
@@ -2984,44 +2949,42 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_update(const double* __restri
       p[sbase + (size_t)o * VB + mp.u] = sv;
       tl.t[rw][mp.jj][mp.u] = sv;
     }
-    tv_tile_store_T<T, VB>(tl, pT + sbase, N, i0, j0);
-    return;
-  }
-  for (int rw = mp.isub; rw < TvMap<VB>::TI; rw += TvMap<VB>::RPI) {
-    const int i = i0 + rw, j = j0 + mp.jj;
-    if (i >= N || j >= N) continue;
-    const int o = i * N + j;
-    T sv = T(0);
-    if (live) {
-      double gx, gy, ux, uy, ndx, ndy, e0, e1;
-      if constexpr (UIN) {
-        const double u0 = din[2 * vo + o], u1 = din[2 * vo + npix + o];
-        double d0, d1;
-        shrink2(u0, u1, tau, kind, d0, d1);
-        e0 = u0 - d0;
-        e1 = u1 - d1;
-      } else {
-        e0 = ev[o];
-        e1 = ev[npix + o];
+  } else {
+    // the last round: d', e' at the tile's pixels, and the diagnostics' sample copy of x
+    for (int rw = mp.isub; rw < TI; rw += Map::RPI) {
+      const int i = i0 + rw, j = j0 + mp.jj;
+      if (i >= N || j >= N) continue;
+      const int o = i * N + j;
+      T sv = T(0);
+      if (live) {
+        double e0, e1, gx, gy, ndx, ndy;  // (of this round's input only e enters)
+        if constexpr (UIN) {
+          const double u0 = din[2 * vo + o], u1 = din[2 * vo + npix + o];
+          double d0, d1;
+          shrink2(u0, u1, tau, kind, d0, d1);
+          e0 = u0 - d0;
+          e1 = u1 - d1;
+        } else {
+          e0 = ev[o];
+          e1 = ev[npix + o];
+        }
+        gradx(mp.u, i, j, gx, gy);
+        const double ux = gx + e0, uy = gy + e1;
+        shrink2(ux, uy, tau, kind, ndx, ndy);
+        const double nex = ux - ndx, ney = uy - ndy;
+        dout[2 * vo + o] = ndx;
+        dout[2 * vo + npix + o] = ndy;
+        eout[2 * vo + o] = nex;
+        eout[2 * vo + npix + o] = ney;
+        const double xn = xat(mp.u, i, j);
+        xout[vo + o] = xn;
+        sv = (T)xn;
       }
-      gradx(mp.u, xv, i, j, gx, gy);
-      ux = gx + e0;
-      uy = gy + e1;
-      shrink2(ux, uy, tau, kind, ndx, ndy);
-      const double nex = ux - ndx, ney = uy - ndy;
-      dout[2 * vo + o] = ndx;
-      dout[2 * vo + npix + o] = ndy;
-      eout[2 * vo + o] = nex;
-      eout[2 * vo + npix + o] = ney;
-      // (LAST only: the other rounds returned above) the diagnostics' sample copy of x
-      const double xn = xat(mp.u, xv, i, j);
-      if constexpr (FUSE) xout[vo + o] = xn;
-      sv = (T)xn;
+      p[sbase + (size_t)o * VB + mp.u] = sv;
+      tl.t[rw][mp.jj][mp.u] = sv;
     }
-    p[sbase + (size_t)o * VB + mp.u] = sv;
-    tl.t[rw][mp.jj][mp.u] = sv;
   }
-  tv_tile_store_T<T, VB>(tl, pT + sbase, N, i0, j0);
+  tile_store_T<T, VB, TI, kTvTile, kTvThreads>(tl, pT + sbase, N, i0, j0);
 }
 
 // node-major float64 [V][L] -> interleaved samples [C][L][VB] of type T, times scale in T: the

@@ -1,5 +1,5 @@
 """GPU: the edge-phase side kernels give bit for bit what tests/golden/edge_phase_parent.json holds
--- recorded on an MI355X (tests/golden/make_edge_phase_golden.py) from the library before its
+-- recorded on an MI355X (tests/golden/make_parent_golden.py) from the library before its
 block reduction, row-sum kernel and projection body were folded into one each (csrc/common.hpp,
 k_bound_project<RELAXED>).  Every float64 sum is compared as its bit pattern, every output array
 by its SHA-256 digest.  The other files hold these sums to 1e-13 / 1e-11 only; here the shapes also
@@ -25,6 +25,10 @@ from test_gpu_relax import _edge_case, _relaxed
 pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edge_phase_parent.json")
+FIXTURE_NOTES = dict(
+    inputs="seeded: test_gpu_bounds._kernel_case, test_gpu_relax._edge_case, metrics_ref.phantom "
+           "(test_gpu_edge_phase_fixture.run_case)",
+    sums="float64 bit patterns, big-endian hex, row-major")
 ALPHA = 1.6
 # pixels: under one block; one block + a 65-pixel tail; 257 blocks, so that thread 0 of the row-sum
 # kernel takes a second slot
