@@ -47,6 +47,8 @@ from .solver import node_ray_weights
 from ._lib import NODE_STATS as _NODE_STATS
 from .matrix import MatrixOperator, as_operators
 from .relax import check_relaxation, check_relaxed_run
+from .penalty import (NORM_KEYS, NORM_STATS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
+                      incidences, thresholds)
 from .metrics import check_data_range, check_metrics, check_side, _check_mask_shape
 
 HISTORY_KEYS = (
@@ -94,9 +96,32 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
              pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
-             metrics_mask=None, relaxation=None, bounds=None, bound_weight=None, return_feasible=False,
-             ray_weights=None):
-    """``relaxation``: None (default) or alpha in the open interval (0, 2): over-relaxation of the
+             metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
+             bound_weight=None, return_feasible=False, ray_weights=None):
+    """``adapt_rho``: None / False (default: one fixed rho), True, or a dict with any of ``ratio`` (10, > 1),
+    ``factor`` (2, > 1), ``every`` (1), ``until`` (None: always; else no change after that many
+    iterations), ``rho_min`` / ``rho_max`` (rho / 1024, rho * 1024): residual balancing (Boyd et al.
+    3.4.1).  After iteration k (when (k + 1) % every == 0 and k + 1 <= until) rho is multiplied by factor
+    where r > ratio * s and divided by it where s > ratio * r, clamped to [rho_min, rho_max]; r, s are
+    ``primal``, ``dual`` (with bounds sqrt(primal^2 + bound_primal^2), sqrt(dual^2 + bound_dual^2)); a
+    residual that is not finite changes nothing.  A change rescales the scaled duals by rho_old /
+    rho_new (exact for factor 2) and re-records the batches' launch sequences (RankGroups.set_rho,
+    admm_batch_set_rho); every rank derives the same rho from the same table.  ``dual``, ``bound_dual``
+    and ``dual_per_node`` use the rho the iteration ran with; the history gains ``rho_history`` (that
+    rho, one per iteration).  From rho_0 a factor 400 off it needs fewer iterations than the hand-tuned
+    rho.  Works with either edge state.  Bad values raise ValueError on the host.
+    ``eps_abs`` / ``eps_rel``: None (default: the absolute test ``eps_pri`` / ``eps_dual``) or finite reals
+    >= 0, not both 0: the scale-free stop test of Boyd et al. (3.12) replaces the absolute one
+    (``eps_pri`` / ``eps_dual`` are then not consulted): stop when r < eps_pri_k and s < eps_dual_k, r and s
+    as above, eps_pri_k = sqrt(n sum_i ninc_i) eps_abs + eps_rel max(||Ax||, ||Bz||), eps_dual_k =
+    sqrt(n V_total) eps_abs + eps_rel ||A^T y||, ninc_i = node i's incidences (degree, + 1 with bounds),
+    the norms those of the stacked constraint after the iteration's edge updates and projection
+    (admm_node_norms, three more columns of the node table; penalty.thresholds).  The history gains
+    ``eps_pri_history``, ``eps_dual_history``, ``ax_norm``, ``bz_norm``, ``aty_norm`` (the unscaled dual's:
+    rho_k ||A^T u||).  Needs stored z (ValueError with derived z, forced or chosen by the HBM rule).
+    Either keyword forces the per-iteration read-back (no pipelined mode).  With all three None
+    nothing changes: no launch, no buffer, no history key.
+    ``relaxation``: None (default) or alpha in the open interval (0, 2): over-relaxation of the
     consensus step (Eckstein-Bertsekas; Boyd et al. 3.4.3).  In the z- and y-updates of every edge
     (and in the projection of a run with ``bounds``) x_i is replaced by alpha x_i + (1 - alpha) z_old
     (admm_consensus_relaxed, admm_bound_project_relaxed; either fusion).  The
@@ -176,6 +201,9 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         raise ValueError("return_feasible needs bounds=(lo, hi)")
     relaxation = check_relaxation(relaxation)
     check_relaxed_run(relaxation, edge_state, forced)
+    adapt = check_adapt_rho(adapt_rho, rho)
+    tol = check_stop_tolerances(eps_abs, eps_rel)
+    check_tolerance_run(tol, edge_state, forced)
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through
@@ -202,7 +230,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                     keep_x=inner_tol is None, group=group, streams=streams,  # this loop never writes x itself
                     derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state],
                     ray_weights=ray_weights, bounds=bounds, bound_weight=bound_weight if bounds is not None else None,
-                    relaxation=relaxation)
+                    relaxation=relaxation, stop_norms=tol is not None)
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
     if start is not None:
@@ -216,7 +244,14 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         hist[f"{name}_per_node"], hist[f"{name}_mean"] = [], []
     if bounds is not None:
         hist.update({k: [] for k in BOUND_KEYS})
+    if adapt is not None:
+        hist["rho_history"] = []
+    if tol is not None:
+        hist.update({k: [] for k in NORM_KEYS})
     edges = plan.edges
+    ninc = incidences(edges, V_total, bounds is not None) if tol is not None else None
+    rho_k = rho  # the rho the next iteration runs with (adapt_rho moves it)
+    rho_changes = 0
     have_ph = phantom_true is not None
     if verbose and rank == 0:
         print(f"Max ADMM Iteration in Block-6 B4 Loop = {max_iters}")
@@ -233,7 +268,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     # per iteration, so the next iteration's launches queue behind the current one.  The
     # histories are computed from the same values by the same host code (bitwise equal).
     pipelined = ((eps_pri <= 0 or eps_dual <= 0) and inner_tol is None and snapshot_dir is None
-                 and chunk_snapshot_dir is None and pipeline is not False)
+                 and chunk_snapshot_dir is None and pipeline is not False and adapt is None and tol is None)
     dev_hist = None
     flushed = 0  # iterations of the pipelined statistics already recorded on the host
     for k in range(max_iters):
@@ -254,6 +289,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         if metrics:
             rg.score_images()  # x is final for this iteration: the consensus writes z and y only
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
+        if tol is not None:
+            rg.node_norms()  # z, y (w, f) are final for this iteration
         iters_done = k + 1
         if pipelined:
             flat = rg.stats_device()
@@ -266,16 +303,35 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                                            have_ph, verbose and rank == 0, metrics, bounds is not None)
             continue
         ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))
-        ns, bres = _take_bounds(hist, bounds is not None, _take_metrics(hist, metrics, ns.numpy()), rho)
-        pn, dn = _record(hist, ns, es.numpy(), edges, V_total, rho, lam_tv, et, have_ph)
+        ns, bres = _take_bounds(hist, bounds is not None, _take_metrics(hist, metrics, ns.numpy()), rho_k)
+        ns, norms = _take_norms(tol is not None, ns)
+        pn, dn = _record(hist, ns, es.numpy(), edges, V_total, rho_k, lam_tv, et, have_ph)
         if snapshot_dir is not None and ((k + 1) % snapshot_every == 0):
             _snapshot(snapshot_dir, k, rg, N)
         if verbose and rank == 0 and k % 10 == 0:
             print(f"iter {k}, primal {pn:.3e}, dual {dn:.3e}")
-        if pn < eps_pri and dn < eps_dual and (bres is None or (bres[0] < eps_pri and bres[1] < eps_dual)):
+        if adapt is not None or tol is not None:  # the stacked residuals: the constraint's rows included
+            r_k = pn if bres is None else math.sqrt(pn * pn + bres[0] * bres[0])
+            s_k = dn if bres is None else math.sqrt(dn * dn + bres[1] * bres[1])
+        if adapt is not None:
+            hist["rho_history"].append(float(rho_k))
+        if tol is not None:
+            ep, ed, ax, bz, aty = thresholds(tol[0], tol[1], N * N, ninc, norms, rho_k)
+            for key, val in zip(NORM_KEYS, (ep, ed, ax, bz, aty)):
+                hist[key].append(val)
+            stop = r_k < ep and s_k < ed
+        else:
+            stop = pn < eps_pri and dn < eps_dual and (bres is None or (bres[0] < eps_pri and bres[1] < eps_dual))
+        if stop:
             if verbose and rank == 0:
                 print(f"stopped at iter {k}, primal {pn:.3e}, dual {dn:.3e}")
             break
+        if adapt is not None and k + 1 < max_iters:  # (after the last iteration no update follows)
+            rho_new = balance(rho_k, r_k, s_k, adapt, k)
+            if rho_new != rho_k:
+                rg.set_rho(rho_new)
+                rho_k = rho_new
+                rho_changes += 1
     if pipelined and dev_hist is not None and iters_done > flushed:
         flushed = _flush_pipelined(hist, dev_hist, flushed, iters_done, rg, V_total, edges, rho, lam_tv, have_ph,
                                    verbose and rank == 0, metrics, bounds is not None)
@@ -286,7 +342,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         timing["iters"] = iters_done
         timing["V_total"] = V_total
     if write_params and rank == 0:
-        _write_params(snapshot_dir, rho, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation)
+        _write_params(snapshot_dir, rho_k, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation,
+                      (rho, adapt, rho_changes) if adapt is not None else None)
     if inspect is not None:
         inspect(rg)
     X = rg.images(feasible=bool(return_feasible))
@@ -387,6 +444,16 @@ def _take_bounds(hist, bounded, ns, rho):
     hist["bound_pri_per_node"].append(r2)
     hist["bound_violation_per_node"].append(viol)
     return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), (bp, bd)
+
+
+def _take_norms(on, ns):
+    """Peel the stop test's three node columns X2, Z2, U2 (right after the library's node statistics
+    once the metric and bound columns are taken) off one iteration's node table: (the table without
+    them, the (V_total, 3) norms), or (ns, None) for a run without eps_abs / eps_rel."""
+    if not on:
+        return ns, None
+    c0, c1 = _NODE_STATS, _NODE_STATS + NORM_STATS
+    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), ns[:, c0:c1].copy()
 
 
 def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None,
@@ -518,8 +585,10 @@ def _snapshot(snapshot_dir, k, rg, N):
             plt.close()
 
 
-def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None):
-    """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha)."""
+def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None):
+    """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha; a run with residual
+    balancing passes the rho its last iteration ran with and ``balancing`` = (rho_0, the checked
+    adapt_rho configuration, the number of changes), which becomes one more line)."""
     try:
         log_dir = snapshot_dir if snapshot_dir is not None else os.getcwd()
         os.makedirs(log_dir, exist_ok=True)
@@ -534,6 +603,11 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxati
             f.write(f"Inner iterations (tv x cg) = {tv_iters} x {cg_iters}\n")
             if relaxation is not None:
                 f.write(f"Over-relaxation alpha = {relaxation}\n")
+            if balancing is not None:
+                rho0, cfg, changes = balancing
+                f.write(f"Residual balancing: rho_0 = {rho0}, ratio = {cfg['ratio']}, factor = {cfg['factor']}, "
+                        f"every = {cfg['every']}, until = {cfg['until']}, rho in [{cfg['rho_min']}, "
+                        f"{cfg['rho_max']}], changes = {changes}\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")
     except Exception as e:  # pragma: no cover
         print(f"[WARN] Could not save internal params: {e}")

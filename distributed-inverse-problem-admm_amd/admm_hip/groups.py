@@ -33,6 +33,7 @@ import torch.distributed as dist
 
 from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, need_stored_z, z_is_stored
 from .bounds import check_bound_run, check_bound_weight, check_bounds
+from .penalty import NORM_STATS, check_tolerance_run
 from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
 
@@ -140,8 +141,11 @@ class RankGroups:
     def __init__(self, A_list, G, V_total: int, world: int, rank: int, sinograms, Qij_diag_fn,
                  rho, lam, mu, tv_iters, cg_iters, tv_kind, phantom, fusion="midpoint", Wi_list=None,
                  keep_x=False, group=None, halo=True, streams=1, derive_z=None,
-                 relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
-        """``relaxation``: None or alpha in (0, 2): every batch's edge updates and projection run
+                 stop_norms=False, relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
+        """``stop_norms``: the run takes the three norms of the scale-free stop test after every
+        iteration (``node_norms``; run_admm's eps_abs / eps_rel): three more node columns, and stored z
+        -- derived z, forced or chosen by the HBM rule, raises ValueError on every rank alike.
+        ``relaxation``: None or alpha in (0, 2): every batch's edge updates and projection run
         over-relaxed (NodeBatch; relax.check_relaxation).  It needs stored z: derived z -- forced, or
         chosen by the HBM rule -- raises ValueError, from run-global facts and so on every rank alike.
         ``bounds`` / ``bound_weight``: the box lo <= x <= hi on every image and kappa of
@@ -167,6 +171,8 @@ class RankGroups:
         check_bound_run(self.bounds, fusion, edge_state, forced)
         self.relaxation = check_relaxation(relaxation)
         check_relaxed_run(self.relaxation, edge_state, forced)
+        self.stop_norms = bool(stop_norms)
+        check_tolerance_run(True if self.stop_norms else None, edge_state, forced)
         if not self.plan.local_nodes:
             raise ValueError(f"rank {rank} owns no graph nodes ({V_total} nodes over {world} ranks)")
         self.world = world
@@ -196,7 +202,7 @@ class RankGroups:
         if derive_z is None and fusion == "midpoint":
             derive_z = not z_is_stored(stored_edges_per_rank(A_list, G, V_total, world, streams,
                                                              bound_slots=self.bounds is not None), n0, hbm, fusion)
-            need_stored_z(derive_z, self.bounds is not None, self.relaxation is not None, "run")
+            need_stored_z(derive_z, self.bounds is not None, self.relaxation is not None, "run", self.stop_norms)
         self.derive_z = bool(derive_z) if derive_z is not None else False
         devices = {k[0][2] for k in keys}
         if len(devices) > 1:
@@ -285,6 +291,19 @@ class RankGroups:
     def consensus(self) -> None:
         self._concurrent(lambda nb: nb.consensus())
 
+    def set_rho(self, rho: float) -> None:
+        """Every batch's penalty <- ``rho`` (NodeBatch.set_rho: the scaled duals rescaled, the library's
+        sequences recorded again).  Every rank computes the same rho from the same all-reduced
+        table, so this needs no collective; an edge stored by two batches is rescaled bitwise alike
+        by both."""
+        for nb in self.batches:
+            nb.set_rho(rho)
+
+    def node_norms(self) -> None:
+        """Each batch's ``norm_stats`` <- X2, Z2, U2 of its local nodes after this iteration's edge
+        updates and projection, on the batch's stream (a ``stop_norms`` run)."""
+        self._concurrent(lambda nb: nb.node_norms())
+
     @property
     def overlaps_exchange(self) -> bool:
         """exchange_consensus can run the rank-internal edge updates under the halo exchange:
@@ -332,20 +351,24 @@ class RankGroups:
         self._concurrent(score)
 
     def _node_stats(self, nb):
-        """The batch's node-statistics rows, widened by its metric columns when metrics are on and
-        then by the projection's three sums when the run has bounds."""
+        """The batch's node-statistics rows, widened by its metric columns when metrics are on,
+        then by the projection's three sums when the run has bounds, then by the stop test's three
+        norms (``stop_norms``)."""
         cols = [nb.node_stats]
         if self.metric_names:
             cols.append(nb.metric_cols)
         if self.bounds is not None:
             cols.append(nb.bound_stats)
+        if self.stop_norms:
+            cols.append(nb.norm_stats)
         return torch.cat(cols, 1) if len(cols) > 1 else nb.node_stats
 
     @property
     def node_stat_width(self) -> int:
         """Columns of the node table ``stats_device`` assembles."""
         return (self.batches[0].node_stats.shape[1] + len(self.metric_names)
-                + (self.batches[0].bound_stats.shape[1] if self.bounds is not None else 0))
+                + (self.batches[0].bound_stats.shape[1] if self.bounds is not None else 0)
+                + (NORM_STATS if self.stop_norms else 0))
 
     def stats(self, extra=None):
         """Global node / edge statistics; ``extra`` (rank-local [V, k] numpy, rows in

@@ -216,12 +216,16 @@ def z_is_stored(stored_edges_per_rank, n: int, hbm_bytes: int, fusion: str = "mi
     return stored_edge_state_bytes(stored_edges_per_rank, n) <= fraction * hbm_bytes
 
 
-def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str) -> None:
-    """Bounds and relaxation need stored z: ValueError where the rule above chose derived z for
-    ``scope`` ("run" / "batch"); the bounds' message first, as the constraint rows count as edges."""
+def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str, tolerances: bool = False) -> None:
+    """Bounds, relaxation and the scale-free stop test (``tolerances``: eps_abs / eps_rel) need stored
+    z: ValueError where the rule above chose derived z for ``scope`` ("run" / "batch"); the bounds'
+    message first, as the constraint rows count as edges."""
     if derive_z and bounded:
         raise ValueError(f"bounds need stored z, and this {scope}'s edge state (the constraint rows included) "
                          "does not fit the stored-z rule (plan.z_is_stored)")
     if derive_z and relaxed:
         raise ValueError(f"relaxation needs stored z, and this {scope}'s edge state does not fit the stored-z "
+                         "rule (plan.z_is_stored)")
+    if derive_z and tolerances:
+        raise ValueError(f"eps_abs / eps_rel need stored z, and this {scope}'s edge state does not fit the stored-z "
                          "rule (plan.z_is_stored)")

@@ -17,6 +17,8 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -25,6 +27,7 @@ from . import _lib
 from .bounds import BoundProjector, check_bound_run, check_bound_weight, check_bounds
 from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
                        ray_weights_host, _Ctx)
+from .penalty import NodeNorms
 from .plan import ShardPlan, need_stored_z, z_is_stored
 from .relax import Relaxer, check_relaxation, check_relaxed_run
 
@@ -208,6 +211,9 @@ class NodeBatch:
         self.bound_stats = self.projector.sums if NB else None  # (V, BOUND_STATS), written by the kernel
         # over-relaxation: alpha and the relaxed edge kernel's scratch (None: the plain updates)
         self.relaxer = Relaxer(alpha, n, E, dev) if alpha is not None else None
+        # the stop test's three norms per node (node_norms): scratch and sums made at the first call
+        self.norms = None
+        self.norm_stats = None
         self.params = dict(rho=float(rho), lam=float(lam), mu=float(mu), tv_iters=int(tv_iters),
                            cg_iters=int(cg_iters), tv_kind=tv_kind)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
@@ -288,6 +294,40 @@ class NodeBatch:
         torch.cuda.synchronize(self.dev)
         _lib.check(self.lib.admm_batch_bind(self.ctx.h, C.byref(self.cb)), "admm_batch_bind")
         self._apply_ray_weights()
+
+    def set_rho(self, rho) -> None:
+        """The batch's penalty rho <- ``rho`` (finite, > 0) between two iterations.  The scaled duals
+        stand for the unscaled rho y, so y -- the constraint rows f included -- and y_b are multiplied
+        by rho_old / rho_new (exact for a power of two); z, d, e, atb and mu are untouched.  The
+        library packs rho D again and re-records its sequences (admm_batch_set_rho: weights, forward
+        plan and scratch stay); the next update is bitwise a freshly bound batch's with this rho."""
+        if isinstance(rho, bool) or not isinstance(rho, numbers.Real) or not (math.isfinite(rho) and rho > 0):
+            raise ValueError(f"rho must be a finite real number > 0, got {rho!r}")
+        new, old = float(rho), self.params["rho"]
+        if new == old:
+            return
+        c = old / new
+        self.y.mul_(c)
+        if self.y_b is not None:
+            self.y_b.mul_(c)
+        _lib.check(self.lib.admm_batch_set_rho(self.ctx.h, new, C.c_void_p(self._s())), "admm_batch_set_rho")
+        self.params["rho"] = new
+        self.cb.rho = new
+
+    def node_norms(self) -> torch.Tensor:
+        """``norm_stats`` (V, 3) <- X2 = |x_k|^2, Z2 = sum of |z_e|^2 and U2 = |sum of the scaled duals|^2
+        over node k's incidences (the constraint slot of a batch with bounds included), on the current
+        stream (admm_node_norms; penalty.thresholds turns them into the stop thresholds).  Needs
+        stored z.  The scratch is made at the first call."""
+        if self.z is None:
+            raise ValueError("node_norms needs stored z")
+        if self.norms is None:
+            self.norms = NodeNorms(self.geom.n, self.V, self.dev)
+            self.norm_stats = self.norms.sums
+        n_edges = self.cb.n_edges
+        return self.norms.run(self.x_local, self.y, self.y_b, self.z, self.inc_off,
+                              self.inc_edge if n_edges else None, self.inc_sign if n_edges else None, n_edges,
+                              self._s())
 
     def set_local_images(self, images) -> None:
         """Local rows of x_ext <- ``images[g]`` (float64 (n,) device tensors by global node)."""

@@ -30,6 +30,13 @@ Beyond the reference's surface:
                 fusion="midpoint" and stored z (admm_hip/admm.py, admm_hip/bounds.py)
 * ``bound_weight``  kappa > 0 of the constraint's weight q_c,i = kappa * Wi_list[i] (default 1)
 * ``return_feasible``  True: return the constraint copies w_i, inside the box exactly, not x_i
+* ``adapt_rho``   None (default), True or a dict (ratio, factor, every, until, rho_min, rho_max): residual
+                balancing of rho (Boyd et al. 3.4.1: rho * factor where primal > ratio * dual, rho /
+                factor where dual > ratio * primal, the scaled duals rescaled); adds the history key
+                rho_history (admm_hip/admm.py, admm_hip/penalty.py)
+* ``eps_abs``, ``eps_rel``  None (default) or the tolerances of the scale-free stop test (Boyd et al.
+                3.12), which then replaces eps_pri / eps_dual; adds the history keys eps_pri_history,
+                eps_dual_history, ax_norm, bz_norm, aty_norm; needs stored z
 * ``relaxation``  None (default) or alpha in (0, 2): over-relaxation of the edge updates (x_i replaced
                 by alpha x_i + (1 - alpha) z_old in the z- and y-updates; the projection of ``bounds``
                 too).  1.5 - 1.8 cuts the iterations to a given residual to about 0.6 x; values
@@ -60,7 +67,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_acceleration=1, scs_lookback=10, scs_scale=1e-1,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
-                       phantom_true=None, write_params=True, relaxation=None, bounds=None,
+                       phantom_true=None, write_params=True, adapt_rho=None, eps_abs=None, eps_rel=None,
+                       relaxation=None, bounds=None,
                        bound_weight=None, return_feasible=False, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
     cg = int(cg_iters)
@@ -76,7 +84,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        inner_chunks=chunks,
                        chunk_snapshot_dir=scs_snapshot_dir if chunks is not None else None,
                        chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights, bounds=bounds,
-                       bound_weight=bound_weight, return_feasible=return_feasible, relaxation=relaxation)
+                       bound_weight=bound_weight, return_feasible=return_feasible, relaxation=relaxation,
+                       adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

@@ -39,6 +39,13 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
 * ``bound_weight``  kappa > 0 of the constraint's weight q_c,i = kappa * Wi_list[i] (default 1)
 * ``return_feasible``  True: return the constraint copies w_i, inside the box exactly, not x_i
 
+* ``adapt_rho``   None (default), True or a dict (ratio, factor, every, until, rho_min, rho_max): residual
+                balancing of rho (Boyd et al. 3.4.1: rho * factor where primal > ratio * dual, rho /
+                factor where dual > ratio * primal, the scaled duals rescaled); adds the history key
+                rho_history (admm_hip/admm.py, admm_hip/penalty.py)
+* ``eps_abs``, ``eps_rel``  None (default) or the tolerances of the scale-free stop test (Boyd et al.
+                3.12), which then replaces eps_pri / eps_dual; adds the history keys eps_pri_history,
+                eps_dual_history, ax_norm, bz_norm, aty_norm; needs stored z
 * ``relaxation``  None (default) or alpha in (0, 2): over-relaxation of the edge updates (:210-230
                 with x_i replaced by alpha x_i + (1 - alpha) z_old; the projection of ``bounds``
                 too).  1.5 - 1.8 cuts the iterations to a given residual to about 0.6 x; values
@@ -61,7 +68,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
                        max_inner_updates=10, x_init=None, metrics=None, data_range=None,
-                       metrics_mask=None, relaxation=None, bounds=None, bound_weight=None,
+                       metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None,
+                       bounds=None, bound_weight=None,
                        return_feasible=False, ray_weights=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
     del max_inner_iters  # accepted but unused, as in the reference (_ver2:17)
@@ -74,4 +82,4 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     max_inner_updates=max_inner_updates, x_init=x_init, metrics=metrics,
                     data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights,
                     bounds=bounds, bound_weight=bound_weight, return_feasible=return_feasible,
-                    relaxation=relaxation)
+                    relaxation=relaxation, adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel)

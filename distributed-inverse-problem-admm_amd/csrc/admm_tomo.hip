@@ -1323,6 +1323,34 @@ int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
   return ADMM_OK;
 }
 
+// rho of the bound batch <- rho (residual balancing): what a bind does with rho and
+// nothing else -- rho D packed again by the bind's own launch, the sequences recorded again.  The
+// per-ray weights, the forward plan and all scratch stay.
+int admm_batch_set_rho(admm_ctx* C, double rho, void* stream) {
+  if (!std::isfinite(rho) || !(rho > 0.0)) return fail(ADMM_E_INVALID, "rho must be finite and > 0");
+  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
+  DEVICE_SCOPE(C->device);
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipDeviceSynchronize());
+  C->b.rho = rho;
+  const int V = C->b.V;
+  const size_t npix = C->npix;
+  RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    using T = typename decltype(tt)::type;
+    constexpr int VB = decltype(vbc)::value;
+    const int nch = (V + VB - 1) / VB;
+    hipLaunchKernelGGL((k_pack_d<T, VB>), dim3((unsigned)((npix + 255) / 256), nch), dim3(256), 0, C->cap.s,
+                       C->b.dsum, (T*)C->dsumS.p, (int)npix, V, rho);
+    CHECK_LAUNCH();
+    return ADMM_OK;
+  }));
+  HIPCHK(hipStreamSynchronize(C->cap.s));
+  C->ats_valid = false;  // (one projection more in the next update: the reuse start is not reasoned about)
+  RET(record_graphs(C));
+  HIPCHK(hipDeviceSynchronize());
+  return ADMM_OK;
+}
+
 int admm_batch_atb(admm_ctx* C, double* atb_out, void* stream) {
   if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
   if (!atb_out) return fail(ADMM_E_INVALID, "null atb_out");

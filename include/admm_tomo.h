@@ -395,6 +395,42 @@ int admm_bound_project_relaxed(const double* x, long long x_stride, double* w, d
                                const double* lo_map, const double* hi_map, double lo, double hi, long long n,
                                int nimg, double alpha, double* work, double* out, void* stream);
 
+/* --- residual-balancing rho and the scale-free stop test --- */
+
+/* rho of the bound batch <- rho, finite and > 0 (ADMM_E_INVALID otherwise; ADMM_E_STATE without a bound
+ * batch; both before any device work).  Does what admm_batch_bind does with rho and nothing else: rho D is
+ * packed again as interleaved samples by the bind's own launch, the kept A^T s of an ADMM_BATCH_KEEP_X
+ * batch is dropped (the next update projects x once more) and the batch's sequences are recorded again.
+ * The per-ray weights, the forward plan and all scratch stay.  After it the next admm_node_update is
+ * bitwise the update of a freshly bound batch with this rho holding the same x_ext, d, e, y, z.  The
+ * scaled duals y (and y_b) stand for rho y: rescaling them by rho_old / rho_new is the caller's
+ * (admm_hip/solver.py NodeBatch.set_rho).  Synchronous like admm_batch_bind.  Additive:
+ * ADMM_ABI_VERSION stays 9. */
+int admm_batch_set_rho(admm_ctx* ctx, double rho, void* stream);
+/* The three norms of Boyd et al.'s (3.12) stop thresholds in node-centric form.  For image v < nimg
+ * (x_v = x + v * x_stride doubles, x_stride >= n) and pixel p < n, over the incidences
+ * q = inc_off[v] .. inc_off[v + 1] - 1 in ascending order, every line one IEEE float64 operation:
+ *   e = inc_edge[q],   yv = inc_sign[q] > 0 ? y[e][p] : (y_b ? y_b[e][p] : -y[e][p])
+ *   s += yv,   zz += z[e][p] * z[e][p]                                   (both from +0)
+ *   out[v] = { X2 = sum_p x_v[p]^2,  Z2 = sum_p zz,  U2 = sum_p s * s }
+ * so that for the stacked constraint "x_i - z_e = 0 at both ends of every edge" ||Ax||^2 = sum_i ninc_i
+ * X2_i, ||Bz||^2 = sum_i Z2_i and ||A^T u||^2 = sum_i U2_i (u the scaled dual; ninc_i = node i's
+ * incidences).  y, z (and y_b, or NULL: midpoint fusion) are [n_edges][n]; inc_off has nimg + 1 entries;
+ * a bound constraint's slot is one more incidence (z row w, y row f, sign +1).  Nothing but `work` and
+ * out ([nimg][3]) is written.  The index arrays are device memory: an incidence whose slot lies outside
+ * [0, n_edges) is not dereferenced and that image's three sums are NaN.  inc_edge, inc_sign, y, z may be
+ * NULL only when n_edges == 0.  Layout of admm_bound_project: 1024 pixels per block, grid ceil(n / 1024)
+ * x nimg, 8-byte accesses, 8 (1 + 2 deg) B read per pixel-image.  No atomics: per-block partial sums in
+ * fixed slots of `work` (admm_node_norms_work doubles, caller-owned), then one fixed-order sum per image,
+ * so an image's sums depend neither on nimg, nor on its place in the batch, nor on x_stride.
+ * Context-free, allocates nothing, 1 <= nimg <= 65535, asynchronous on `stream` (current device).
+ * Additive: ADMM_ABI_VERSION stays 9. */
+int admm_node_norms(const double* x, long long x_stride, const double* y, const double* y_b, const double* z,
+                    long long n, int nimg, const int32_t* inc_off, const int32_t* inc_edge,
+                    const int32_t* inc_sign, int n_edges, double* work, double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_node_norms needs for this n and nimg.  No device work. */
+int admm_node_norms_work(long long n, int nimg, long long* n_doubles);
+
 #ifdef __cplusplus
 }
 #endif
