@@ -143,6 +143,16 @@ SYMBOLS = {
     "admm_node_norms": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "admm_node_norms_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_fuse_absmax": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int,
+                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_fuse_absmax_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_fuse_accumulate": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int,
+                             C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "admm_fuse_finish": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
+                         C.c_void_p],
+    "admm_fuse_deviation": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                            C.c_void_p],
+    "admm_fuse_deviation_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
 }
 
 _lock = threading.Lock()

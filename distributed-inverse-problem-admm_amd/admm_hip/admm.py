@@ -40,6 +40,7 @@ import torch.distributed as dist
 
 from .bounds import BOUND_KEYS, BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
 from .exchange import split_stats
+from .fuse import FUSE_KEYS, FUSE_SCALARS, check_fuse
 from .fbp import FILTERS, fbp
 from .geometry import CSR_WEIGHTS_MSG, RayTransform
 from .groups import RankGroups
@@ -95,10 +96,27 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              cg_iters=5, tv_kind="iso", group=None, return_tensors=False, timing=None,
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
-             pipeline=None, streams=1, edge_state=None, x_init=None, metrics=None, data_range=None,
+             pipeline=None, streams=1, edge_state=None, x_init=None, fuse=None, fuse_out=None,
+             metrics=None, data_range=None,
              metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
              bound_weight=None, return_feasible=False, ray_weights=None):
-    """``adapt_rho``: None / False (default: one fixed rho), True, or a dict with any of ``ratio`` (10, > 1),
+    """``fuse``: None (default), "uniform" or "precision": after every iteration's x-update the network's
+    images are fused on the GPU into xbar = (sum_i W_i x_i) / (sum_i W_i) per pixel over all graph nodes
+    (W = Wi_list; "uniform": W = 1, the plain mean) and the history gains ``consensus_err`` =
+    sqrt(sum_i |x_i - xbar|^2) -- unlike ``primal`` independent of the graph and its edge count --,
+    ``consensus_err_per_node`` (|x_i - xbar|, one V_total array per iteration), ``fused_img_mse`` =
+    |xbar - phantom|^2 (a sum like ``img_mse_*``; NaN without a phantom) and, with ``metrics``,
+    ``fused_psnr`` / ``fused_ssim`` of xbar (same data_range and mask).  The sums over nodes are fixed-point
+    (admm_hip/fuse.py, csrc/fuse.hip): exact, so every value is bitwise the same for any rank count, batch
+    split and ``streams``; their resolution is 2 V^2 B 2^-61 with B the largest |W_i x_i| of the network.
+    The values ride in node-table columns, so the pipelined mode keeps its freedom from host
+    synchronisation.  ``fuse_out``: a dict that receives ``"image"`` (the fusion of the returned images: of
+    w_i with ``return_feasible``) and ``"spread"`` (their per-pixel weighted standard deviation across
+    nodes) as (N, N) arrays, or device tensors with ``return_tensors``; bitwise
+    ``admm_hip.fuse_images(x_list, Wi_list, spread=True)``.  Works with every other keyword (the feature
+    only reads images).  Anything else raises ValueError on the host.  With fuse=None nothing changes: no
+    launch, no buffer, no column, no history key, no collective.
+    ``adapt_rho``: None / False (default: one fixed rho), True, or a dict with any of ``ratio`` (10, > 1),
     ``factor`` (2, > 1), ``every`` (1), ``until`` (None: always; else no change after that many
     iterations), ``rho_min`` / ``rho_max`` (rho / 1024, rho * 1024): residual balancing (Boyd et al.
     3.4.1).  After iteration k (when (k + 1) % every == 0 and k + 1 <= until) rho is multiplied by factor
@@ -204,6 +222,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     adapt = check_adapt_rho(adapt_rho, rho)
     tol = check_stop_tolerances(eps_abs, eps_rel)
     check_tolerance_run(tol, edge_state, forced)
+    fuse = check_fuse(fuse)
+    if fuse is None and fuse_out is not None:
+        raise ValueError("fuse_out needs fuse='uniform' or 'precision'")
+    if fuse_out is not None and not isinstance(fuse_out, dict):
+        raise ValueError("fuse_out must be a dict (it is filled like timing)")
+    if fuse == "precision" and Wi_list is None:
+        raise ValueError("fuse='precision' needs Wi_list")
     V_total = len(A_dense_list)
     # matrices (the reference's dense A_dense_list; dense numpy / torch, scipy.sparse)
     # become explicit-matrix operators (matrix.py); operators pass through
@@ -237,6 +262,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         rg.start_from(_initial_images(start, A_dense_list, sinograms, plan.local_nodes, rg.device))
     if metrics:
         rg.enable_metrics(metrics, data_range, metrics_mask)
+    if fuse is not None:
+        rg.enable_fuse(fuse, Wi_list)  # (after the metrics: the fused image is scored like the nodes')
     if world > 1:
         dist.barrier(group=group)
     hist = {k: [] for k in HISTORY_KEYS + EXTRA_KEYS}
@@ -248,6 +275,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         hist["rho_history"] = []
     if tol is not None:
         hist.update({k: [] for k in NORM_KEYS})
+    if fuse is not None:
+        hist.update({k: [] for k in FUSE_KEYS + tuple(f"fused_{m}" for m in metrics or ())})
     edges = plan.edges
     ninc = incidences(edges, V_total, bounds is not None) if tol is not None else None
     rho_k = rho  # the rho the next iteration runs with (adapt_rho moves it)
@@ -288,6 +317,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                 eps_used[rows], n_upd[rows] = _solve_to_reference_tolerance(nb, et, max_inner_updates)
         if metrics:
             rg.score_images()  # x is final for this iteration: the consensus writes z and y only
+        if fuse is not None:
+            rg.fuse_images()
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
         if tol is not None:
             rg.node_norms()  # z, y (w, f) are final for this iteration
@@ -300,11 +331,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             dev_hist[k - flushed].copy_(flat)
             if k + 1 - flushed == dev_hist.shape[0]:  # block full: flush to the host
                 flushed = _flush_pipelined(hist, dev_hist, flushed, k + 1, rg, V_total, edges, rho, lam_tv,
-                                           have_ph, verbose and rank == 0, metrics, bounds is not None)
+                                           have_ph, verbose and rank == 0, metrics, bounds is not None,
+                                           fuse is not None)
             continue
         ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))
         ns, bres = _take_bounds(hist, bounds is not None, _take_metrics(hist, metrics, ns.numpy()), rho_k)
         ns, norms = _take_norms(tol is not None, ns)
+        ns = _take_fuse(hist, fuse is not None, metrics, ns, have_ph)
         pn, dn = _record(hist, ns, es.numpy(), edges, V_total, rho_k, lam_tv, et, have_ph)
         if snapshot_dir is not None and ((k + 1) % snapshot_every == 0):
             _snapshot(snapshot_dir, k, rg, N)
@@ -334,7 +367,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                 rho_changes += 1
     if pipelined and dev_hist is not None and iters_done > flushed:
         flushed = _flush_pipelined(hist, dev_hist, flushed, iters_done, rg, V_total, edges, rho, lam_tv, have_ph,
-                                   verbose and rank == 0, metrics, bounds is not None)
+                                   verbose and rank == 0, metrics, bounds is not None, fuse is not None)
     torch.cuda.synchronize()
     if timing is not None:
         import time
@@ -343,9 +376,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         timing["V_total"] = V_total
     if write_params and rank == 0:
         _write_params(snapshot_dir, rho_k, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation,
-                      (rho, adapt, rho_changes) if adapt is not None else None)
+                      (rho, adapt, rho_changes) if adapt is not None else None, fuse)
     if inspect is not None:
         inspect(rg)
+    if fuse is not None and fuse_out is not None:  # the returned images' fusion and spread: after the loop's clock
+        xbar, sp = rg.fused_image(feasible=bool(return_feasible), spread=True)
+        for key, t in (("image", xbar), ("spread", sp)):
+            fuse_out[key] = t.view(N, N) if return_tensors else t.to("cpu").numpy().reshape(N, N)
     X = rg.images(feasible=bool(return_feasible))
     if return_tensors:
         return [X[i] for i in range(V_total)], hist
@@ -456,8 +493,25 @@ def _take_norms(on, ns):
     return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), ns[:, c0:c1].copy()
 
 
+def _take_fuse(hist, on, metrics, ns, have_ph):
+    """Record the fusion's columns (right after the library's node statistics once the metric, bound and norm
+    columns are taken) of one iteration's node table: |x_i - xbar|^2 per node, then -- in the row of global
+    node 0 only -- |xbar - phantom|^2 and the fused image's metrics.  Returns the table without them."""
+    if not on:
+        return ns
+    c0 = _NODE_STATS
+    c1 = c0 + 1 + FUSE_SCALARS + len(metrics or ())
+    dev2 = ns[:, c0].copy()
+    hist["consensus_err"].append(math.sqrt(float(np.sum(dev2))))
+    hist["consensus_err_per_node"].append(np.sqrt(dev2))
+    hist["fused_img_mse"].append(float(ns[0, c0 + 1]) if have_ph else float("nan"))
+    for j, name in enumerate(metrics or ()):
+        hist[f"fused_{name}"].append(float(ns[0, c0 + 1 + FUSE_SCALARS + j]))
+    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1)
+
+
 def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None,
-                     bounded=False):
+                     bounded=False, fused=False):
     """Record iterations k0 .. k1-1 of the pipelined statistics (rows 0 .. k1-k0-1 of
     ``dev_hist``) on the host; returns k1."""
     host = dev_hist[: k1 - k0].to("cpu")
@@ -466,6 +520,7 @@ def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, ha
     for k in range(k0, k1):
         ns, es = split_stats(host[k - k0], V_total, nsw, len(edges), rg.batches[0].edge_stats.shape[1])
         ns, _ = _take_bounds(hist, bounded, _take_metrics(hist, metrics, ns.numpy()), rho)
+        ns = _take_fuse(hist, fused, metrics, ns, have_ph)
         pn, dn = _record(hist, np.concatenate([ns, extra], axis=1), es.numpy(),
                          edges, V_total, rho, lam_tv, eps_target(k), have_ph)
         if verbose and k % 10 == 0:
@@ -585,7 +640,7 @@ def _snapshot(snapshot_dir, k, rg, N):
             plt.close()
 
 
-def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None):
+def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None, fuse=None):
     """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha; a run with residual
     balancing passes the rho its last iteration ran with and ``balancing`` = (rho_0, the checked
     adapt_rho configuration, the number of changes), which becomes one more line)."""
@@ -608,6 +663,8 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxati
                 f.write(f"Residual balancing: rho_0 = {rho0}, ratio = {cfg['ratio']}, factor = {cfg['factor']}, "
                         f"every = {cfg['every']}, until = {cfg['until']}, rho in [{cfg['rho_min']}, "
                         f"{cfg['rho_max']}], changes = {changes}\n")
+            if fuse is not None:
+                f.write(f"Fused image = {fuse} mean over the nodes\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")
     except Exception as e:  # pragma: no cover
         print(f"[WARN] Could not save internal params: {e}")

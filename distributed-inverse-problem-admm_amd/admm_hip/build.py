@@ -10,7 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(_HERE)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(_HERE, "libadmm_tomo.so")
-SOURCES = ["admm_tomo.hip", "masks.hip", "fbp.hip", "metrics.hip", "bounds.hip", "relax.hip", "norms.hip"]
+SOURCES = ["admm_tomo.hip", "masks.hip", "fbp.hip", "metrics.hip", "bounds.hip", "relax.hip", "norms.hip",
+           "fuse.hip"]
 DEPS = SOURCES + ["kernels.hpp", "tables.hpp", "fwd_plan.hpp", "common.hpp"]
 
 

@@ -110,12 +110,17 @@ class HaloExchange:
 
 
 def _all_reduce_sum(t: torch.Tensor, group=None) -> torch.Tensor:
+    return all_reduce(t, dist.ReduceOp.SUM, group)
+
+
+def all_reduce(t: torch.Tensor, op, group=None) -> torch.Tensor:
+    """``t`` all-reduced in place with ``op`` (gloo: staged through a host copy)."""
     if t.is_cuda and dist.get_backend(group) == "gloo":
         host = t.cpu()
-        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(host, op=op, group=group)
         t.copy_(host)
     else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(t, op=op, group=group)
     return t
 
 

@@ -28,7 +28,7 @@ import warnings
 
 import torch
 
-from .exchange import HaloExchange, assemble_stats_device, assemble_stats_parts, gather_images_parts
+from .exchange import HaloExchange, all_reduce, assemble_stats_device, assemble_stats_parts, gather_images_parts
 import torch.distributed as dist
 
 from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, need_stored_z, z_is_stored
@@ -193,6 +193,7 @@ class RankGroups:
                 streams = 1
         self.streams_requested = streams
         self.metric_names = ()  # enable_metrics
+        self.fuse_mode = None  # enable_fuse
         bs = rank_batches(A_list, self.plan, streams)
         keys = [k for k, _ in bs]
         members = dict(bs)
@@ -339,6 +340,7 @@ class RankGroups:
         and batch derives the same L and pixel counts from the same phantom and mask."""
         from .metrics import Scorer
         self.metric_names = tuple(names)
+        self._metric_mask = mask
         for nb in self.batches:
             nb.scorer = Scorer(nb.phantom, data_range, mask, device=nb.device, max_images=nb.V)
             nb.metric_cols = None
@@ -350,10 +352,112 @@ class RankGroups:
             nb.metric_cols = nb.scorer.columns(nb.x_local, self.metric_names)
         self._concurrent(score)
 
+    def enable_fuse(self, mode, Wi_list=None) -> None:
+        """Fuse the network's images from now on (fuse.check_fuse modes; ``fuse_images``): every batch gets
+        a fuse.Fuser and, for "precision", its local nodes' rows of ``Wi_list`` as a [V][n] device tensor
+        (weighted fusion's ``nb.w`` covers x_ext rows and exists only there); the rank gets the int64
+        accumulators, the fused image and -- with a phantom -- the scratch of |xbar - phantom|^2 and of the
+        fused image's metrics (a Scorer of its own: the batches' run on their streams).  Dn = fixed_sum(W)
+        is static and formed here, once.  Collective over the ranks of a distributed run."""
+        from .fuse import FUSE_SCALARS, TERM_W, FixedSum, Fuser, check_fuse
+        from .solver import _as_f64_tensor
+        self.fuse_mode = check_fuse(mode)
+        if self.fuse_mode is None:
+            return
+        if self.fuse_mode == "precision" and Wi_list is None:
+            raise ValueError("fuse='precision' needs Wi_list")
+        n = self.batches[0].x_ext.shape[1]
+        dev = self.batches[0].dev
+        for nb in self.batches:
+            nb.fuser = Fuser(n, nb.V, dev)
+            nb.fuse_w = (torch.stack([_as_f64_tensor(Wi_list[g], n, dev) for g in nb.plan.local_nodes])
+                         if self.fuse_mode == "precision" else None)
+            # the rank-replicated scalars ride in the row of global node 0 and are zero elsewhere
+            nb.fuse_scalars = torch.zeros((nb.V, FUSE_SCALARS + len(self.metric_names)), dtype=torch.float64,
+                                          device=dev)
+        self._fuse_owner = next(((nb, nb.plan.local_nodes.index(0)) for nb in self.batches
+                                 if 0 in nb.plan.local_nodes), None)
+        self._fuse_one = Fuser(n, 1, dev)  # one-image launches: finish, |xbar - phantom|^2
+        self._fuse_num = FixedSum(n, dev)
+        self._fuse_var = None  # the spread's sum, made when asked for
+        self.fused = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._fuse_se = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._fuse_scorer = None
+        if self.metric_names:
+            from .metrics import Scorer
+            nb0 = self.batches[0]
+            self._fuse_scorer = Scorer(nb0.phantom, nb0.scorer.data_range, self._metric_mask, device=nb0.device,
+                                       max_images=1)
+        self._fuse_den = None
+        if self.fuse_mode == "precision":
+            self._fuse_den = FixedSum(n, dev)
+            self._fixed_sum(self._fuse_den, TERM_W, [(nb, None) for nb in self.batches], None)
+
+    def _fixed_sum(self, fs, mode, parts, mean) -> None:
+        """``fs`` <- fixed_sum of the terms ``mode`` over ALL graph nodes, ``parts`` = [(batch, its image
+        rows)] being this rank's: every batch's absmax, the MAX over ranks, every batch's accumulate into the
+        rank's one accumulator, the int64 SUM over ranks.  All on the current stream, one batch after the
+        other -- the accumulator has one writer at a time, and the integer sum is exact in any order."""
+        fs.zero_()
+        for nb, x in parts:
+            nb.fuser.absmax(x, nb.fuse_w, mean, mode, fs)
+        if self.world > 1 and self.halo is not None:
+            all_reduce(fs.bmax, dist.ReduceOp.MAX, self.group)
+        for nb, x in parts:
+            nb.fuser.accumulate(x, nb.fuse_w, mean, mode, fs, self.plan.V_total)
+        if self.world > 1 and self.halo is not None:
+            all_reduce(fs.acc, dist.ReduceOp.SUM, self.group)
+
+    def _fuse(self, rows, out) -> None:
+        from .fuse import TERM_WX
+        self._fixed_sum(self._fuse_num, TERM_WX, [(nb, rows(nb)) for nb in self.batches], None)
+        self._fuse_one.finish(self._fuse_num, self._fuse_den, self.plan.V_total, out)
+
+    def fuse_images(self) -> None:
+        """``fused`` <- the fusion of every node's current image, bitwise the same on every rank and for every
+        batch split; each batch's ``fuser.dev2`` <- |x_i - xbar|^2 of its local nodes, and the row of global
+        node 0 of ``fuse_scalars`` <- |xbar - phantom|^2 and the fused image's metrics.  Call where
+        ``score_images`` is called: x is final for the iteration.  No host synchronisation (RCCL; gloo
+        stages through the host).  Collective over the ranks of a distributed run."""
+        self._fuse(lambda nb: nb.x_local, self.fused)
+        for nb in self.batches:
+            nb.fuser.deviation(nb.x_local, self.fused)
+        nb0 = self.batches[0]
+        if nb0.phantom is None or self._fuse_owner is None:
+            return
+        own, r = self._fuse_owner
+        self._fuse_one.deviation(self.fused.view(1, -1), nb0.phantom, out=self._fuse_se)
+        own.fuse_scalars[r, 0:1].copy_(self._fuse_se)
+        if self._fuse_scorer is not None:
+            own.fuse_scalars[r, 1:].copy_(self._fuse_scorer.columns(self.fused.view(1, -1), self.metric_names)[0])
+
+    def fused_image(self, feasible: bool = False, spread: bool = False):
+        """(xbar, spread or None) of the current images -- ``feasible`` (a run with bounds): of the constraint
+        copies w_i, a convex combination of box-feasible images, clipped to the box so that a last-ulp
+        rounding of the quotient cannot leave it -- as fresh (n,) device tensors."""
+        from .fuse import TERM_WD2, FixedSum
+        if feasible and self.bounds is None:
+            raise ValueError("feasible images need bounds")
+        rows = (lambda nb: nb.w_bound) if feasible else (lambda nb: nb.x_local)
+        mean = torch.empty_like(self.fused)
+        self._fuse(rows, mean)
+        if feasible:
+            # Nn and Dn are rounded independently, so where every w_i sits on a bound their quotient may
+            # leave the box by an ulp: the promise "inside the box exactly" is kept by the box's own clip
+            mean = self.batches[0].projector.clip(mean.view(1, -1)).reshape(-1).contiguous()
+        if not spread:
+            return mean, None
+        if self._fuse_var is None:
+            self._fuse_var = FixedSum(mean.numel(), mean.device)
+        self._fixed_sum(self._fuse_var, TERM_WD2, [(nb, rows(nb)) for nb in self.batches], mean)
+        sp = self._fuse_one.finish(self._fuse_var, self._fuse_den, self.plan.V_total, torch.empty_like(mean), root=True)
+        return mean, sp
+
     def _node_stats(self, nb):
         """The batch's node-statistics rows, widened by its metric columns when metrics are on,
         then by the projection's three sums when the run has bounds, then by the stop test's three
-        norms (``stop_norms``)."""
+        norms (``stop_norms``), then by the fusion's columns (``enable_fuse``): |x_i - xbar|^2 and the
+        rank-replicated scalars, which only the row of global node 0 carries."""
         cols = [nb.node_stats]
         if self.metric_names:
             cols.append(nb.metric_cols)
@@ -361,14 +465,22 @@ class RankGroups:
             cols.append(nb.bound_stats)
         if self.stop_norms:
             cols.append(nb.norm_stats)
+        if self.fuse_mode is not None:
+            cols.extend([nb.fuser.dev2.view(-1, 1), nb.fuse_scalars])
         return torch.cat(cols, 1) if len(cols) > 1 else nb.node_stats
+
+    @property
+    def fuse_width(self) -> int:
+        """The fusion's node-table columns: dev2, |xbar - phantom|^2 and one per metric; 0 when off."""
+        from .fuse import FUSE_SCALARS
+        return 1 + FUSE_SCALARS + len(self.metric_names) if self.fuse_mode is not None else 0
 
     @property
     def node_stat_width(self) -> int:
         """Columns of the node table ``stats_device`` assembles."""
         return (self.batches[0].node_stats.shape[1] + len(self.metric_names)
                 + (self.batches[0].bound_stats.shape[1] if self.bounds is not None else 0)
-                + (NORM_STATS if self.stop_norms else 0))
+                + (NORM_STATS if self.stop_norms else 0) + self.fuse_width)
 
     def stats(self, extra=None):
         """Global node / edge statistics; ``extra`` (rank-local [V, k] numpy, rows in

@@ -42,6 +42,13 @@ Beyond the reference's surface:
                 too).  1.5 - 1.8 cuts the iterations to a given residual to about 0.6 x; values
                 near 2 oscillate with the inexact x-update.  Needs stored z; None and 1.0 change
                 nothing (admm_hip/admm.py, admm_hip/relax.py)
+* ``fuse``      None (default), "uniform" or "precision": the network's fused image xbar = (sum_i W_i
+                x_i) / (sum_i W_i) over all nodes (W = Wi_list, or 1) after every iteration, on the GPU with
+                exact fixed-point sums (bitwise the same for any rank count and batch split); adds the
+                history keys consensus_err, consensus_err_per_node, fused_img_mse and, with metrics,
+                fused_psnr / fused_ssim (admm_hip/admm.py, admm_hip/fuse.py)
+* ``fuse_out``  a dict that receives "image" (the fusion of the returned images) and "spread" (their
+                per-pixel weighted standard deviation across nodes) as (N, N) arrays
 """
 from __future__ import annotations
 
@@ -67,8 +74,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_acceleration=1, scs_lookback=10, scs_scale=1e-1,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
-                       phantom_true=None, write_params=True, adapt_rho=None, eps_abs=None, eps_rel=None,
-                       relaxation=None, bounds=None,
+                       phantom_true=None, write_params=True, fuse=None, fuse_out=None,
+                       adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
                        bound_weight=None, return_feasible=False, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
     cg = int(cg_iters)
@@ -85,7 +92,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        chunk_snapshot_dir=scs_snapshot_dir if chunks is not None else None,
                        chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights, bounds=bounds,
                        bound_weight=bound_weight, return_feasible=return_feasible, relaxation=relaxation,
-                       adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel)
+                       adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel, fuse=fuse, fuse_out=fuse_out)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

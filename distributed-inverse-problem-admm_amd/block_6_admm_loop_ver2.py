@@ -51,6 +51,13 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 too).  1.5 - 1.8 cuts the iterations to a given residual to about 0.6 x; values
                 near 2 oscillate with the inexact x-update.  Needs stored z; None and 1.0 change
                 nothing (admm_hip/admm.py, admm_hip/relax.py)
+* ``fuse``      None (default), "uniform" or "precision": the network's fused image xbar = (sum_i W_i
+                x_i) / (sum_i W_i) over all nodes (W = Wi_list, or 1) after every iteration, on the GPU with
+                exact fixed-point sums (bitwise the same for any rank count and batch split); adds the
+                history keys consensus_err, consensus_err_per_node, fused_img_mse and, with metrics,
+                fused_psnr / fused_ssim (admm_hip/admm.py, admm_hip/fuse.py)
+* ``fuse_out``  a dict that receives "image" (the fusion of the returned images) and "spread" (their
+                per-pixel weighted standard deviation across nodes) as (N, N) arrays
 
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
@@ -67,8 +74,9 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        snapshot_every=None, snapshot_div=10, phantom_true=None,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
-                       max_inner_updates=10, x_init=None, metrics=None, data_range=None,
-                       metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None,
+                       max_inner_updates=10, x_init=None, fuse=None, fuse_out=None,
+                       metrics=None, data_range=None, metrics_mask=None,
+                       adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None,
                        bounds=None, bound_weight=None,
                        return_feasible=False, ray_weights=None):
     """Returns (x_list, history) like block_6_admm_loop_ver2.py:310-326."""
@@ -82,4 +90,5 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     max_inner_updates=max_inner_updates, x_init=x_init, metrics=metrics,
                     data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights,
                     bounds=bounds, bound_weight=bound_weight, return_feasible=return_feasible,
-                    relaxation=relaxation, adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel)
+                    relaxation=relaxation, adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel,
+                    fuse=fuse, fuse_out=fuse_out)

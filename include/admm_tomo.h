@@ -431,6 +431,61 @@ int admm_node_norms(const double* x, long long x_stride, const double* y, const 
 /* *n_doubles = the doubles of `work` admm_node_norms needs for this n and nimg.  No device work. */
 int admm_node_norms_work(long long n, int nimg, long long* n_doubles);
 
+/* --- the network-fused image and the consensus error --- */
+
+/* The fused image xbar = (sum_i w_i x_i) / (sum_i w_i) per pixel over ALL v_total graph nodes (w = 1: the
+ * plain mean) is built from sums over nodes that live in different batches, streams and ranks.  They are
+ * fixed-point sums: exact, hence the same bits in any order and grouping.  fixed_sum(t) of terms t_i[p]
+ * over all v_total nodes and p < n, every line one IEEE float64 operation:
+ *   B = max_{i,p} |t_i[p]|                   (a NaN or +-inf term: B = +inf, and every output is NaN)
+ *   B == 0: s = 0;  else B = m 2^e with 0.5 <= m < 1 (frexp), L = bit_length(v_total - 1), s = 61 - e - L
+ *   q_i[p] = llrint(ldexp(t_i[p], s))        (|q| <= 2^(61 - L): v_total of them fit int64)
+ *   S[p]   = sum_i q_i[p]                    (int64: exact, associative)
+ *   fixed_sum[p] = ldexp((double)S[p], -s)   (the conversion rounds to nearest even)
+ * and   Nn = fixed_sum(w x),  Dn = fixed_sum(w) (v_total for w = 1),  xbar = Nn / Dn,
+ *       spread = sqrt(fixed_sum(w ((x - xbar) (x - xbar))) / Dn),  dev2_i = sum_p (x_i[p] - xbar[p])^2.
+ * Resolution: all pixels share the grid 2^-s, so a sum is within v_total 2^-s <= 2 v_total^2 B 2^-61 of the
+ * exact sum of its terms: relative to the largest term of the whole network, not to the pixel (one wild
+ * pixel coarsens every pixel's grid; with B within a few powers of two of the typical values the grid is
+ * finer than double).
+ * Across batches B chains through admm_fuse_absmax and S through admm_fuse_accumulate; across ranks B is a
+ * MAX all-reduce of one double and S an int64 SUM all-reduce of n values.  `mode` selects the terms:
+ * 0: w x,  1: w,  2: w ((x - m) (x - m)) with m [n]; w == NULL is w = 1 (x * 1 = x, so the same bits); x may
+ * be NULL in mode 1.  Image v is x + v * x_stride (x_stride >= n), its weights w + v * w_stride.  Layout of
+ * admm_bound_project: 256 threads, 1024 pixels per block, 8-byte accesses; no atomics.  All entry points:
+ * context-free, allocate nothing, 1 <= nimg <= 65535, 1 <= v_total <= 2^30, arguments checked before any
+ * HIP call (ADMM_E_INVALID), asynchronous on `stream` (current device).  Additive: ADMM_ABI_VERSION stays 9. */
+
+/* out[0] <- max(out[0], max_{v < nimg, p < n} |t_v[p]|), a term that is not finite counting as +inf (and a
+ * NaN already in out[0] becoming +inf): start from out[0] = 0 and call once per batch.  Grid ceil(n / 1024) x
+ * nimg, each block's maximum to its slot of `work` (admm_fuse_absmax_work doubles), then one block folds
+ * the slots into out[0].  Reads 8 B (16 B with w) per pixel-image. */
+int admm_fuse_absmax(const double* x, long long x_stride, const double* w, long long w_stride, const double* m,
+                     long long n, int nimg, int mode, double* work, double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_fuse_absmax needs for this n and nimg.  No device work. */
+int admm_fuse_absmax_work(long long n, int nimg, long long* n_doubles);
+/* acc[p] += sum_{v < nimg} q_v[p] with s derived on the device from bmax[0] = the B of ALL v_total nodes (a
+ * device pointer: the host never reads B) -- start from acc = 0 and call once per batch, in any order.  One
+ * thread per pixel loops over the images, four images' loads in flight together.  bmax[0] not finite: acc is
+ * left alone (admm_fuse_finish writes NaN).  A term larger than bmax[0] is the caller's error.  nimg <=
+ * v_total.  Reads 8 B (16 B with w) per pixel-image, 8 B read and written per pixel. */
+int admm_fuse_accumulate(const double* x, long long x_stride, const double* w, long long w_stride, const double* m,
+                         long long n, int nimg, int mode, const double* bmax, int v_total, int64_t* acc,
+                         void* stream);
+/* out[p] = fixed_sum_num[p] / fixed_sum_den[p] (root != 0: its sqrt, the spread) from the accumulators and
+ * the B they were formed with; acc_den == bmax_den == NULL: the denominator is (double)v_total (w = 1).  If
+ * a B is not finite every out[p] is NaN. */
+int admm_fuse_finish(const int64_t* acc_num, const double* bmax_num, const int64_t* acc_den, const double* bmax_den,
+                     int v_total, long long n, int root, double* out, void* stream);
+/* out[v] = sum_p (x_v[p] - mean[p])^2 for v < nimg: per-block sums in fixed slots of `work`
+ * (admm_fuse_deviation_work doubles), then one fixed-order sum per image, as admm_node_norms does -- an
+ * image's sum depends neither on nimg, nor on its place in the batch, nor on x_stride.  Nothing but `work`
+ * and out is written. */
+int admm_fuse_deviation(const double* x, long long x_stride, const double* mean, long long n, int nimg, double* work,
+                        double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_fuse_deviation needs for this n and nimg.  No device work. */
+int admm_fuse_deviation_work(long long n, int nimg, long long* n_doubles);
+
 #ifdef __cplusplus
 }
 #endif
