@@ -189,3 +189,21 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().admm_last_error().decode(errors="replace")
         raise AdmmError(f"{what} failed (rc={rc}): {msg}")
+
+
+def ptr(t) -> C.c_void_p:
+    """The data pointer of the tensor ``t`` as a C argument; None is the null pointer."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def work_size(fn_name: str, *args) -> int:
+    """Doubles of scratch the library's size query ``fn_name`` (an ``admm_*_work`` entry point) asks for."""
+    need = C.c_longlong()
+    check(getattr(load(), fn_name)(*args, C.byref(need)), fn_name)
+    return need.value
+
+
+def work_buffer(fn_name: str, *args, device):
+    """The caller-owned float64 scratch of a kernel: ``work_size(fn_name, *args)`` doubles on ``device``."""
+    import torch
+    return torch.empty(work_size(fn_name, *args), dtype=torch.float64, device=device)

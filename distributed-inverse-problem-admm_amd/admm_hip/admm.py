@@ -38,27 +38,21 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .bounds import BOUND_KEYS, BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
+from .bounds import BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
 from .exchange import split_stats
-from .fuse import FUSE_KEYS, FUSE_SCALARS, check_fuse
+from .fuse import FUSE_SCALARS, check_fuse
 from .fbp import FILTERS, fbp
 from .geometry import CSR_WEIGHTS_MSG, RayTransform
 from .groups import RankGroups
 from .solver import node_ray_weights
-from ._lib import NODE_STATS as _NODE_STATS
+from ._lib import EDGE_STATS
 from .matrix import MatrixOperator, as_operators
 from .relax import check_relaxation, check_relaxed_run
-from .penalty import (NORM_KEYS, NORM_STATS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
+from .penalty import (NORM_KEYS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
                       incidences, thresholds)
+from .table import DZ2, G2, IMG, MSE_SINO, QUAD, RA2, RB2, SBRES2, TV
+from .table import EXTRA_KEYS, HISTORY_KEYS  # noqa: F401  (the core block's keys; importers find them here)
 from .metrics import check_data_range, check_metrics, check_side, _check_mask_shape
-
-HISTORY_KEYS = (
-    "primal", "dual", "pri_per_node", "dual_per_node", "obj_per_node", "obj_total",
-    "mse_sino_per_node", "mse_sino_total", "img_mse_per_node", "img_mse_total",
-    "g_norm_history", "eps_used_history", "eps_target_history",
-)
-
-EXTRA_KEYS = ("sb_res_history", "inner_updates_history")
 
 DEFAULT_MU_FACTOR = 10.0  # split-Bregman penalty mu = 10 * lam_tv
 EPS_CAP, CALIB_ALPHA, MAX_TIGHTEN = 1e-2, 1.0, 2  # block_6_admm_loop_ver2.py:106-113
@@ -266,22 +260,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         rg.enable_fuse(fuse, Wi_list)  # (after the metrics: the fused image is scored like the nodes')
     if world > 1:
         dist.barrier(group=group)
-    hist = {k: [] for k in HISTORY_KEYS + EXTRA_KEYS}
-    for name in metrics or ():
-        hist[f"{name}_per_node"], hist[f"{name}_mean"] = [], []
-    if bounds is not None:
-        hist.update({k: [] for k in BOUND_KEYS})
+    hist = {}
+    record = _Recorder(hist, rg.columns, plan.edges, V_total, lam_tv, phantom_true is not None, metrics,
+                       incidences(plan.edges, V_total, bounds is not None) if tol is not None else None, tol, N * N)
     if adapt is not None:
-        hist["rho_history"] = []
-    if tol is not None:
-        hist.update({k: [] for k in NORM_KEYS})
-    if fuse is not None:
-        hist.update({k: [] for k in FUSE_KEYS + tuple(f"fused_{m}" for m in metrics or ())})
-    edges = plan.edges
-    ninc = incidences(edges, V_total, bounds is not None) if tol is not None else None
+        hist["rho_history"] = []  # (the loop's own key, after the blocks': the dict's order is no promise)
     rho_k = rho  # the rho the next iteration runs with (adapt_rho moves it)
     rho_changes = 0
-    have_ph = phantom_true is not None
     if verbose and rank == 0:
         print(f"Max ADMM Iteration in Block-6 B4 Loop = {max_iters}")
     torch.cuda.synchronize()
@@ -330,15 +315,11 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                                        device=flat.device)
             dev_hist[k - flushed].copy_(flat)
             if k + 1 - flushed == dev_hist.shape[0]:  # block full: flush to the host
-                flushed = _flush_pipelined(hist, dev_hist, flushed, k + 1, rg, V_total, edges, rho, lam_tv,
-                                           have_ph, verbose and rank == 0, metrics, bounds is not None,
-                                           fuse is not None)
+                flushed = _flush_pipelined(record, dev_hist, flushed, k + 1, rho, verbose and rank == 0)
             continue
-        ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))
-        ns, bres = _take_bounds(hist, bounds is not None, _take_metrics(hist, metrics, ns.numpy()), rho_k)
-        ns, norms = _take_norms(tol is not None, ns)
-        ns = _take_fuse(hist, fuse is not None, metrics, ns, have_ph)
-        pn, dn = _record(hist, ns, es.numpy(), edges, V_total, rho_k, lam_tv, et, have_ph)
+        ns, es = rg.stats(np.stack([eps_used, n_upd], axis=1))  # (the loop's two columns, gathered with the table)
+        ns, w = ns.numpy(), rg.columns.width
+        pn, dn, bres, eps = record(k, ns[:, :w], es.numpy(), rho_k, ns[:, w], ns[:, w + 1])
         if snapshot_dir is not None and ((k + 1) % snapshot_every == 0):
             _snapshot(snapshot_dir, k, rg, N)
         if verbose and rank == 0 and k % 10 == 0:
@@ -349,10 +330,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         if adapt is not None:
             hist["rho_history"].append(float(rho_k))
         if tol is not None:
-            ep, ed, ax, bz, aty = thresholds(tol[0], tol[1], N * N, ninc, norms, rho_k)
-            for key, val in zip(NORM_KEYS, (ep, ed, ax, bz, aty)):
-                hist[key].append(val)
-            stop = r_k < ep and s_k < ed
+            stop = r_k < eps[0] and s_k < eps[1]
         else:
             stop = pn < eps_pri and dn < eps_dual and (bres is None or (bres[0] < eps_pri and bres[1] < eps_dual))
         if stop:
@@ -366,8 +344,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                 rho_k = rho_new
                 rho_changes += 1
     if pipelined and dev_hist is not None and iters_done > flushed:
-        flushed = _flush_pipelined(hist, dev_hist, flushed, iters_done, rg, V_total, edges, rho, lam_tv, have_ph,
-                                   verbose and rank == 0, metrics, bounds is not None, fuse is not None)
+        flushed = _flush_pipelined(record, dev_hist, flushed, iters_done, rho, verbose and rank == 0)
     torch.cuda.synchronize()
     if timing is not None:
         import time
@@ -452,120 +429,101 @@ def _check_metric_args(metrics, data_range, metrics_mask, phantom_true, N):
     return metrics
 
 
-def _take_metrics(hist, metrics, ns):
-    """Record the metric columns (right after the library's node statistics) of one iteration's
-    node table and return the table without them -- the table of a run without metrics."""
-    if not metrics:
-        return ns
-    c0, c1 = _NODE_STATS, _NODE_STATS + len(metrics)
-    for j, name in enumerate(metrics):
-        col = ns[:, c0 + j].copy()
-        hist[f"{name}_per_node"].append(col)
-        hist[f"{name}_mean"].append(float(np.mean(col)))
-    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1)
+class _Recorder:
+    """One run's histories: made once with what is constant over the run, then called once per iteration
+    with the global statistics tables -- by the live loop and by the pipelined flush alike.  The node
+    table's blocks are read through the run's layout (table.NodeColumns), which also names the history
+    keys of every block.  ``ninc`` / ``tol`` / ``n_pixels``: the stop test's incidences (penalty.incidences),
+    (eps_abs, eps_rel) and pixels per image -- a layout with the ``norms`` block needs them."""
+
+    def __init__(self, hist, cols, edges, V_total, lam_tv, have_ph, metrics, ninc=None, tol=None, n_pixels=None):
+        self.hist, self.cols, self.edges, self.V_total = hist, cols, edges, V_total
+        self.lam_tv, self.have_ph, self.metrics = lam_tv, have_ph, tuple(metrics or ())
+        self.ninc, self.tol, self.n_pixels = ninc, tol, n_pixels
+        for block in cols.blocks:
+            hist.update({k: [] for k in block.keys})
+
+    def __call__(self, k, ns, es, rho, eps_used=None, n_upd=None):
+        """Append iteration ``k``'s histories from the global tables ``ns`` (V_total x the layout's width)
+        and ``es`` (edges x EDGE_STATS), ``rho`` being the rho the iteration ran with.  ``eps_used`` /
+        ``n_upd``: the loop's own two per-node columns; None (the pipelined mode, which applies no
+        tolerance) records NaN and 1.  Returns (primal, dual, (bound_primal, bound_dual) or None,
+        (eps_pri_k, eps_dual_k) or None)."""
+        hist, V_total = self.hist, self.V_total
+        v = self.cols.split(ns)
+        bres = eps = None
+        if "metrics" in v:
+            for j, name in enumerate(self.metrics):
+                col = v["metrics"][:, j].copy()
+                hist[f"{name}_per_node"].append(col)
+                hist[f"{name}_mean"].append(float(np.mean(col)))
+        if "bounds" in v:  # the projection's three sums
+            r2, dw2, viol = (v["bounds"][:, j].copy() for j in range(BOUND_STATS))
+            bres = (math.sqrt(float(np.sum(r2))), rho * math.sqrt(float(np.sum(dw2))))  # the form of ``dual``
+            hist["bound_primal"].append(bres[0])
+            hist["bound_dual"].append(bres[1])
+            hist["bound_violation"].append(math.sqrt(float(np.sum(viol))))
+            hist["bound_pri_per_node"].append(r2)
+            hist["bound_violation_per_node"].append(viol)
+        if "norms" in v:  # X2, Z2, U2 -> the stop thresholds
+            vals = thresholds(self.tol[0], self.tol[1], self.n_pixels, self.ninc, v["norms"].copy(), rho)
+            for key, val in zip(NORM_KEYS, vals):
+                hist[key].append(val)
+            eps = vals[:2]
+        if "fuse" in v:  # |x_i - xbar|^2 per node, then -- in the row of global node 0 only -- the scalars
+            dev2 = v["fuse"][:, 0].copy()
+            hist["consensus_err"].append(math.sqrt(float(np.sum(dev2))))
+            hist["consensus_err_per_node"].append(np.sqrt(dev2))
+            hist["fused_img_mse"].append(float(v["fuse"][0, 1]) if self.have_ph else float("nan"))
+            for j, name in enumerate(self.metrics):
+                hist[f"fused_{name}"].append(float(v["fuse"][0, 1 + FUSE_SCALARS + j]))
+        # --- node diagnostics (_ver2:145-206) ---
+        core = v["core"]
+        mse = core[:, MSE_SINO].copy()
+        obj = 0.5 * core[:, MSE_SINO] + self.lam_tv * core[:, TV] + core[:, QUAD]
+        hist["g_norm_history"].append(np.sqrt(core[:, G2]))
+        hist["eps_used_history"].append(np.full(V_total, np.nan) if eps_used is None else eps_used.copy())
+        hist["eps_target_history"].append(np.full(V_total, eps_target(k)))
+        hist["sb_res_history"].append(np.sqrt(core[:, SBRES2]))
+        hist["inner_updates_history"].append((np.ones(V_total) if n_upd is None else n_upd).astype(np.int64))
+        hist["mse_sino_per_node"].append(mse)
+        hist["mse_sino_total"].append(float(np.sum(mse)))
+        img = core[:, IMG].copy() if self.have_ph else np.full(V_total, np.nan)
+        hist["img_mse_per_node"].append(img)
+        hist["img_mse_total"].append(float(np.sum(img)))
+        # --- residuals in G.edges() order (_ver2:232-258) ---
+        r2 = 0.0
+        s2 = 0.0
+        pri = np.zeros(V_total)
+        dua = np.zeros(V_total)
+        for ge, (a, b) in enumerate(self.edges):
+            ra2, rb2, dz2 = float(es[ge, RA2]), float(es[ge, RB2]), float(es[ge, DZ2])
+            r2 += ra2 + rb2
+            pri[a] += ra2
+            pri[b] += rb2
+            s2 += rho * rho * dz2
+            dua[a] += rho * rho * dz2
+            dua[b] += rho * rho * dz2
+        pn, dn = math.sqrt(r2), math.sqrt(s2)
+        hist["primal"].append(pn)
+        hist["dual"].append(dn)
+        hist["obj_per_node"].append(obj)
+        hist["obj_total"].append(float(np.sum(obj)))
+        hist["pri_per_node"].append(np.sqrt(pri))
+        hist["dual_per_node"].append(np.sqrt(dua))
+        return pn, dn, bres, eps
 
 
-def _take_bounds(hist, bounded, ns, rho):
-    """Record the projection's three sums (the columns right after the library's node statistics
-    once the metric columns are taken) of one iteration's node table; returns the table without
-    them and (bound_primal, bound_dual), or (ns, None) for a run without bounds."""
-    if not bounded:
-        return ns, None
-    c0, c1 = _NODE_STATS, _NODE_STATS + BOUND_STATS
-    r2, dw2, viol = (ns[:, c0 + j].copy() for j in range(BOUND_STATS))
-    bp = math.sqrt(float(np.sum(r2)))
-    bd = rho * math.sqrt(float(np.sum(dw2)))  # the form _record uses for ``dual``
-    hist["bound_primal"].append(bp)
-    hist["bound_dual"].append(bd)
-    hist["bound_violation"].append(math.sqrt(float(np.sum(viol))))
-    hist["bound_pri_per_node"].append(r2)
-    hist["bound_violation_per_node"].append(viol)
-    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), (bp, bd)
-
-
-def _take_norms(on, ns):
-    """Peel the stop test's three node columns X2, Z2, U2 (right after the library's node statistics
-    once the metric and bound columns are taken) off one iteration's node table: (the table without
-    them, the (V_total, 3) norms), or (ns, None) for a run without eps_abs / eps_rel."""
-    if not on:
-        return ns, None
-    c0, c1 = _NODE_STATS, _NODE_STATS + NORM_STATS
-    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1), ns[:, c0:c1].copy()
-
-
-def _take_fuse(hist, on, metrics, ns, have_ph):
-    """Record the fusion's columns (right after the library's node statistics once the metric, bound and norm
-    columns are taken) of one iteration's node table: |x_i - xbar|^2 per node, then -- in the row of global
-    node 0 only -- |xbar - phantom|^2 and the fused image's metrics.  Returns the table without them."""
-    if not on:
-        return ns
-    c0 = _NODE_STATS
-    c1 = c0 + 1 + FUSE_SCALARS + len(metrics or ())
-    dev2 = ns[:, c0].copy()
-    hist["consensus_err"].append(math.sqrt(float(np.sum(dev2))))
-    hist["consensus_err_per_node"].append(np.sqrt(dev2))
-    hist["fused_img_mse"].append(float(ns[0, c0 + 1]) if have_ph else float("nan"))
-    for j, name in enumerate(metrics or ()):
-        hist[f"fused_{name}"].append(float(ns[0, c0 + 1 + FUSE_SCALARS + j]))
-    return np.concatenate([ns[:, :c0], ns[:, c1:]], axis=1)
-
-
-def _flush_pipelined(hist, dev_hist, k0, k1, rg, V_total, edges, rho, lam_tv, have_ph, verbose, metrics=None,
-                     bounded=False, fused=False):
+def _flush_pipelined(record, dev_hist, k0, k1, rho, verbose):
     """Record iterations k0 .. k1-1 of the pipelined statistics (rows 0 .. k1-k0-1 of
     ``dev_hist``) on the host; returns k1."""
     host = dev_hist[: k1 - k0].to("cpu")
-    nsw = rg.node_stat_width
-    extra = np.stack([np.full(V_total, np.nan), np.ones(V_total)], axis=1)
     for k in range(k0, k1):
-        ns, es = split_stats(host[k - k0], V_total, nsw, len(edges), rg.batches[0].edge_stats.shape[1])
-        ns, _ = _take_bounds(hist, bounded, _take_metrics(hist, metrics, ns.numpy()), rho)
-        ns = _take_fuse(hist, fused, metrics, ns, have_ph)
-        pn, dn = _record(hist, np.concatenate([ns, extra], axis=1), es.numpy(),
-                         edges, V_total, rho, lam_tv, eps_target(k), have_ph)
+        ns, es = split_stats(host[k - k0], record.V_total, record.cols.width, len(record.edges), EDGE_STATS)
+        pn, dn, _, _ = record(k, ns.numpy(), es.numpy(), rho)
         if verbose and k % 10 == 0:
             print(f"iter {k}, primal {pn:.3e}, dual {dn:.3e}")
     return k1
-
-
-def _record(hist, ns, es, edges, V_total, rho, lam_tv, et, have_ph):
-    """Append one iteration's histories from the global statistics tables (nodes x 8, edges x 3);
-    returns (primal, dual)."""
-    # --- node diagnostics (_ver2:145-206) ---
-    mse = ns[:, 0].copy()
-    g_norm = np.sqrt(ns[:, 1])
-    obj = 0.5 * ns[:, 0] + lam_tv * ns[:, 2] + ns[:, 3]
-    hist["g_norm_history"].append(g_norm)
-    hist["eps_used_history"].append(ns[:, 6].copy())
-    hist["eps_target_history"].append(np.full(V_total, et))
-    hist["sb_res_history"].append(np.sqrt(ns[:, 5]))
-    hist["inner_updates_history"].append(ns[:, 7].astype(np.int64))
-    hist["mse_sino_per_node"].append(mse)
-    hist["mse_sino_total"].append(float(np.sum(mse)))
-    img = ns[:, 4].copy() if have_ph else np.full(V_total, np.nan)
-    hist["img_mse_per_node"].append(img)
-    hist["img_mse_total"].append(float(np.sum(img)))
-    # --- residuals in G.edges() order (_ver2:232-258) ---
-    r2 = 0.0
-    s2 = 0.0
-    pri = np.zeros(V_total)
-    dua = np.zeros(V_total)
-    for ge, (a, b) in enumerate(edges):
-        ra2, rb2, dz2 = float(es[ge, 0]), float(es[ge, 1]), float(es[ge, 2])
-        r2 += ra2 + rb2
-        pri[a] += ra2
-        pri[b] += rb2
-        s2 += rho * rho * dz2
-        dua[a] += rho * rho * dz2
-        dua[b] += rho * rho * dz2
-    pn, dn = math.sqrt(r2), math.sqrt(s2)
-    hist["primal"].append(pn)
-    hist["dual"].append(dn)
-    hist["obj_per_node"].append(obj)
-    hist["obj_total"].append(float(np.sum(obj)))
-    hist["pri_per_node"].append(np.sqrt(pri))
-    hist["dual_per_node"].append(np.sqrt(dua))
-    return pn, dn
 
 
 def _solve_to_reference_tolerance(nb, et, max_inner_updates):

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .plan import derived_z_requested
 
 BOUND_STATS = 3  # |x - w'|^2, |w' - w|^2, |x - clip(x)|^2
 BOUND_KEYS = ("bound_primal", "bound_dual", "bound_violation", "bound_pri_per_node", "bound_violation_per_node")
@@ -104,7 +105,7 @@ def check_bound_run(bounds, fusion: str, edge_state, env_edge_state: str = ""):
         return
     if fusion != "midpoint":
         raise ValueError("bounds need fusion='midpoint' (the constraint slot has one dual)")
-    if edge_state == "derived" or (edge_state is None and env_edge_state == "derived"):
+    if derived_z_requested(edge_state, env_edge_state):
         raise ValueError("bounds need stored z (edge_state='stored'): the constraint variable w is a stored z row")
 
 
@@ -119,9 +120,7 @@ class BoundProjector:
         self.max_images = int(max_images)
         dev = torch.device("cuda", device) if isinstance(device, int) else device
         self.dev = dev
-        need = C.c_longlong()
-        _lib.check(self.lib.admm_bound_project_work(self.n, self.max_images, C.byref(need)), "admm_bound_project_work")
-        self.work = torch.empty(need.value, dtype=torch.float64, device=dev)
+        self.work = _lib.work_buffer("admm_bound_project_work", self.n, self.max_images, device=dev)
         self.sums = torch.zeros((self.max_images, BOUND_STATS), dtype=torch.float64, device=dev)
         put = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
         self.lo_map, self.hi_map = put(bounds.lo_map), put(bounds.hi_map)
@@ -147,7 +146,7 @@ class BoundProjector:
                 raise ValueError(f"{name}: rows must be contiguous and must not overlap")
         if nimg > 1 and w.stride(0) != f.stride(0):
             raise ValueError("w and f must share one row stride")
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        p = _lib.ptr
         xs = x.stride(0) if nimg > 1 else self.n
         ws = w.stride(0) if nimg > 1 else self.n
         box = (p(x), xs, p(w), p(f), ws, p(self.lo_map), p(self.hi_map), float(self.bounds.lo), float(self.bounds.hi),

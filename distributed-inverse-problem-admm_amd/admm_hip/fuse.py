@@ -42,8 +42,7 @@ def check_fuse(fuse):
     return fuse
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+_p = _lib.ptr
 
 
 def _rows(t, nimg, n, what):
@@ -75,11 +74,9 @@ class Fuser:
         self.lib = _lib.load()
         self.n, self.nimg = int(n), int(nimg)
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        need = C.c_longlong()
-        _lib.check(self.lib.admm_fuse_absmax_work(self.n, self.nimg, C.byref(need)), "admm_fuse_absmax_work")
-        k = need.value
-        _lib.check(self.lib.admm_fuse_deviation_work(self.n, self.nimg, C.byref(need)), "admm_fuse_deviation_work")
-        self.work = torch.empty(max(k, need.value), dtype=torch.float64, device=self.dev)
+        need = max(_lib.work_size(fn, self.n, self.nimg)
+                   for fn in ("admm_fuse_absmax_work", "admm_fuse_deviation_work"))
+        self.work = torch.empty(need, dtype=torch.float64, device=self.dev)  # one scratch serves both launches
         self.dev2 = torch.zeros(self.nimg, dtype=torch.float64, device=self.dev)
 
     def new_sum(self) -> FixedSum:

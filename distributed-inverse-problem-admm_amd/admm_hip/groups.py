@@ -32,10 +32,12 @@ from .exchange import HaloExchange, all_reduce, assemble_stats_device, assemble_
 import torch.distributed as dist
 
 from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan, need_stored_z, z_is_stored
-from .bounds import check_bound_run, check_bound_weight, check_bounds
-from .penalty import NORM_STATS, check_tolerance_run
+from .bounds import BOUND_KEYS, BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
+from .fuse import FUSE_KEYS, FUSE_SCALARS, TERM_W, TERM_WD2, TERM_WX, FixedSum, Fuser, check_fuse
+from .penalty import NORM_KEYS, NORM_STATS, check_tolerance_run
 from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
+from .table import NodeColumns
 
 
 def operator_key(A):
@@ -194,6 +196,12 @@ class RankGroups:
         self.streams_requested = streams
         self.metric_names = ()  # enable_metrics
         self.fuse_mode = None  # enable_fuse
+        # the node table's columns (table.py); enable_metrics and enable_fuse widen it
+        self.columns = NodeColumns()
+        if self.bounds is not None:
+            self.columns.add("bounds", BOUND_STATS, lambda nb: [nb.bound_stats], BOUND_KEYS)
+        if self.stop_norms:
+            self.columns.add("norms", NORM_STATS, lambda nb: [nb.norm_stats], NORM_KEYS)
         bs = rank_batches(A_list, self.plan, streams)
         keys = [k for k, _ in bs]
         members = dict(bs)
@@ -341,6 +349,10 @@ class RankGroups:
         from .metrics import Scorer
         self.metric_names = tuple(names)
         self._metric_mask = mask
+        self.columns.remove("metrics")
+        if self.metric_names:  # (no name: no column, nothing to concatenate)
+            self.columns.add("metrics", len(self.metric_names), lambda nb: [nb.metric_cols],
+                             tuple(k for m in self.metric_names for k in (f"{m}_per_node", f"{m}_mean")))
         for nb in self.batches:
             nb.scorer = Scorer(nb.phantom, data_range, mask, device=nb.device, max_images=nb.V)
             nb.metric_cols = None
@@ -359,15 +371,18 @@ class RankGroups:
         accumulators, the fused image and -- with a phantom -- the scratch of |xbar - phantom|^2 and of the
         fused image's metrics (a Scorer of its own: the batches' run on their streams).  Dn = fixed_sum(W)
         is static and formed here, once.  Collective over the ranks of a distributed run."""
-        from .fuse import FUSE_SCALARS, TERM_W, FixedSum, Fuser, check_fuse
         from .solver import _as_f64_tensor
         self.fuse_mode = check_fuse(mode)
+        self.columns.remove("fuse")
         if self.fuse_mode is None:
             return
         if self.fuse_mode == "precision" and Wi_list is None:
             raise ValueError("fuse='precision' needs Wi_list")
         n = self.batches[0].x_ext.shape[1]
         dev = self.batches[0].dev
+        self.columns.add("fuse", 1 + FUSE_SCALARS + len(self.metric_names),
+                         lambda nb: [nb.fuser.dev2.view(-1, 1), nb.fuse_scalars],
+                         FUSE_KEYS + tuple(f"fused_{m}" for m in self.metric_names))
         for nb in self.batches:
             nb.fuser = Fuser(n, nb.V, dev)
             nb.fuse_w = (torch.stack([_as_f64_tensor(Wi_list[g], n, dev) for g in nb.plan.local_nodes])
@@ -409,7 +424,6 @@ class RankGroups:
             all_reduce(fs.acc, dist.ReduceOp.SUM, self.group)
 
     def _fuse(self, rows, out) -> None:
-        from .fuse import TERM_WX
         self._fixed_sum(self._fuse_num, TERM_WX, [(nb, rows(nb)) for nb in self.batches], None)
         self._fuse_one.finish(self._fuse_num, self._fuse_den, self.plan.V_total, out)
 
@@ -435,7 +449,6 @@ class RankGroups:
         """(xbar, spread or None) of the current images -- ``feasible`` (a run with bounds): of the constraint
         copies w_i, a convex combination of box-feasible images, clipped to the box so that a last-ulp
         rounding of the quotient cannot leave it -- as fresh (n,) device tensors."""
-        from .fuse import TERM_WD2, FixedSum
         if feasible and self.bounds is None:
             raise ValueError("feasible images need bounds")
         rows = (lambda nb: nb.w_bound) if feasible else (lambda nb: nb.x_local)
@@ -454,33 +467,20 @@ class RankGroups:
         return mean, sp
 
     def _node_stats(self, nb):
-        """The batch's node-statistics rows, widened by its metric columns when metrics are on,
-        then by the projection's three sums when the run has bounds, then by the stop test's three
-        norms (``stop_norms``), then by the fusion's columns (``enable_fuse``): |x_i - xbar|^2 and the
-        rank-replicated scalars, which only the row of global node 0 carries."""
-        cols = [nb.node_stats]
-        if self.metric_names:
-            cols.append(nb.metric_cols)
-        if self.bounds is not None:
-            cols.append(nb.bound_stats)
-        if self.stop_norms:
-            cols.append(nb.norm_stats)
-        if self.fuse_mode is not None:
-            cols.extend([nb.fuser.dev2.view(-1, 1), nb.fuse_scalars])
+        """The batch's rows of the node table: its ``columns`` side by side (table.py states the order);
+        ``nb.node_stats`` itself, no device work, when no feature widens the table."""
+        cols = self.columns.sources(nb)
         return torch.cat(cols, 1) if len(cols) > 1 else nb.node_stats
 
     @property
     def fuse_width(self) -> int:
         """The fusion's node-table columns: dev2, |xbar - phantom|^2 and one per metric; 0 when off."""
-        from .fuse import FUSE_SCALARS
-        return 1 + FUSE_SCALARS + len(self.metric_names) if self.fuse_mode is not None else 0
+        return self.columns.width_of("fuse")
 
     @property
     def node_stat_width(self) -> int:
         """Columns of the node table ``stats_device`` assembles."""
-        return (self.batches[0].node_stats.shape[1] + len(self.metric_names)
-                + (self.batches[0].bound_stats.shape[1] if self.bounds is not None else 0)
-                + (NORM_STATS if self.stop_norms else 0) + self.fuse_width)
+        return self.columns.width
 
     def stats(self, extra=None):
         """Global node / edge statistics; ``extra`` (rank-local [V, k] numpy, rows in

@@ -140,12 +140,9 @@ class Scorer:
         self._reserve(max_images)
 
     def _reserve(self, nimg: int) -> None:
-        import torch
         if nimg <= self._cap:
             return
-        k = C.c_longlong()
-        _lib.check(self.lib.admm_image_metrics_work(self.N, int(nimg), C.byref(k)), "admm_image_metrics_work")
-        self._work = torch.empty(k.value, dtype=torch.float64, device=self.dev)
+        self._work = _lib.work_buffer("admm_image_metrics_work", self.N, int(nimg), device=self.dev)
         self._cap = nimg
 
     def sums(self, x):
@@ -159,7 +156,7 @@ class Scorer:
             x = x.contiguous()
         self._reserve(V)
         out = torch.empty((V, 2), dtype=torch.float64, device=self.dev)
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
+        p = _lib.ptr
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.admm_image_metrics(p(x), int(x.stride(0)) if V > 1 else self.n, p(self.ref), p(self.mask),
                                                    self.N, V, self.c1, self.c2, p(self._work), p(out),

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .plan import derived_z_requested
 
 NORM_STATS = 3  # X2, Z2, U2
 NORM_KEYS = ("eps_pri_history", "eps_dual_history", "ax_norm", "bz_norm", "aty_norm")
@@ -122,7 +123,7 @@ def check_tolerance_run(tol, edge_state, env_edge_state: str = ""):
     norm ||Bz|| reads the stored z rows, which a derived-z run does not have."""
     if tol is None:
         return
-    if edge_state == "derived" or (edge_state is None and env_edge_state == "derived"):
+    if derived_z_requested(edge_state, env_edge_state):
         raise ValueError("eps_abs / eps_rel need stored z (edge_state='stored'): the stop thresholds read "
                          "||z|| from the stored edge rows")
 
@@ -158,9 +159,7 @@ class NodeNorms:
         self.lib = _lib.load()
         self.n = int(n)
         self.nimg = int(nimg)
-        need = C.c_longlong()
-        _lib.check(self.lib.admm_node_norms_work(self.n, self.nimg, C.byref(need)), "admm_node_norms_work")
-        self.work = torch.empty(need.value, dtype=torch.float64, device=device)
+        self.work = _lib.work_buffer("admm_node_norms_work", self.n, self.nimg, device=device)
         self.sums = torch.zeros((self.nimg, NORM_STATS), dtype=torch.float64, device=device)
 
     def run(self, x, y, y_b, z, inc_off, inc_edge, inc_sign, n_edges: int, stream: int) -> torch.Tensor:
@@ -173,7 +172,7 @@ class NodeNorms:
                 raise ValueError(f"{name} must be contiguous and hold {n_edges} rows of {self.n} doubles")
         if inc_off.numel() < self.nimg + 1:
             raise ValueError(f"inc_off needs {self.nimg + 1} entries, got {inc_off.numel()}")
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        p = _lib.ptr
         _lib.check(self.lib.admm_node_norms(p(x), int(x.stride(0)), p(y), p(y_b), p(z), self.n, self.nimg, p(inc_off),
                                             p(inc_edge), p(inc_sign), int(n_edges), p(self.work), p(self.sums),
                                             C.c_void_p(stream)), "admm_node_norms")

@@ -216,6 +216,12 @@ def z_is_stored(stored_edges_per_rank, n: int, hbm_bytes: int, fusion: str = "mi
     return stored_edge_state_bytes(stored_edges_per_rank, n) <= fraction * hbm_bytes
 
 
+def derived_z_requested(edge_state, env_edge_state: str = "") -> bool:
+    """The caller asks for derived z: ``edge_state`` (run_admm's keyword) says so, or leaves it open (None)
+    and the environment's ADMM_EDGE_STATE, ``env_edge_state``, forces it."""
+    return edge_state == "derived" or (edge_state is None and env_edge_state == "derived")
+
+
 def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str, tolerances: bool = False) -> None:
     """Bounds, relaxation and the scale-free stop test (``tolerances``: eps_abs / eps_rel) need stored
     z: ValueError where the rule above chose derived z for ``scope`` ("run" / "batch"); the bounds'

@@ -21,6 +21,7 @@ import numbers
 import torch
 
 from . import _lib
+from .plan import derived_z_requested
 
 
 def check_relaxation(relaxation) -> float | None:
@@ -42,7 +43,7 @@ def check_relaxed_run(alpha, edge_state, env_edge_state: str = ""):
     the midpoint of the endpoint images of the last consensus, which a relaxed z' is not."""
     if alpha is None:
         return
-    if edge_state == "derived" or (edge_state is None and env_edge_state == "derived"):
+    if derived_z_requested(edge_state, env_edge_state):
         raise ValueError("relaxation needs stored z (edge_state='stored'): a relaxed z is not the midpoint of "
                          "the endpoint images, so it cannot be derived from them")
 
@@ -56,17 +57,14 @@ class Relaxer:
         self.alpha = float(alpha)
         self.n = int(n)
         self.n_edges = int(n_edges)
-        need = C.c_longlong()
-        _lib.check(self.lib.admm_consensus_relaxed_work(self.n, self.n_edges, C.byref(need)),
-                   "admm_consensus_relaxed_work")
-        self.work = torch.empty(need.value, dtype=torch.float64, device=device)
+        self.work = _lib.work_buffer("admm_consensus_relaxed_work", self.n, self.n_edges, device=device)
 
     def run_edges(self, nb, e0: int, e1: int, stream: int) -> None:
         """y, z (weighted fusion: y_b too) and ``edge_stats`` of ``nb``'s edge slots [e0, e1) <- the
         relaxed update around its x_ext, in place, on ``stream``."""
         if not (0 <= e0 <= e1 <= self.n_edges):
             raise ValueError(f"edge slots [{e0}, {e1}) outside the batch's [0, {self.n_edges})")
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        p = _lib.ptr
         _lib.check(self.lib.admm_consensus_relaxed(p(nb.x_ext), self.n, nb.x_ext.shape[0], p(nb.y), p(nb.y_b),
                                                    p(nb.z), p(nb.w), p(nb.edge_a), p(nb.edge_b), int(e0), int(e1),
                                                    self.alpha, p(self.work), p(nb.edge_stats), C.c_void_p(stream)),

@@ -216,7 +216,7 @@ class NodeBatch:
         self.norm_stats = None
         self.params = dict(rho=float(rho), lam=float(lam), mu=float(mu), tv_iters=int(tv_iters),
                            cg_iters=int(cg_iters), tv_kind=tv_kind)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        p = _lib.ptr
         self.cb = _lib.Batch(
             V, plan.n_xext, ES, int(tv_iters), int(cg_iters),
             _lib.ADMM_TV_ANISO if tv_kind == "aniso" else _lib.ADMM_TV_ISO,

@@ -319,3 +319,40 @@ def test_pipelined_statistics_equal_per_iteration_readback(cuda):
         assert all(np.array_equal(a, b) for a, b in zip(x1, x2))
         for k in h1:
             assert np.array_equal(np.asarray(h1[k]), np.asarray(h2[k]), equal_nan=True), k
+
+
+def every_block_run(**kw):
+    """N = 48, the 5-node unequal-angle split (two device batches), ring graph, 3 iterations with every
+    node-table block on: metrics, bounds, over-relaxation, the fused image.  rho = 1.7, not a power of two: a
+    product with one is exact in any grouping, and the histories' rho arithmetic would go unchecked."""
+    from admm_hip.admm import run_admm
+    ops, ph, sinos, Wi, Q, A, _ = setup_problem(48, 5, 192)
+    return run_admm(ops, sinos, nx.cycle_graph(5), Wi, Q, 48, lam_tv=0.02, rho=1.7, max_iters=3, eps_pri=0.0,
+                    eps_dual=0.0, verbose=False, phantom_true=ph, write_params=False, metrics=("psnr", "ssim"),
+                    bounds=(0, None), relaxation=1.6, fuse="precision", **kw)
+
+
+def test_every_table_block_at_once(cuda):
+    """Every feature that adds node-table columns in one run.  (1) The pipelined statistics equal the
+    per-iteration read-back bitwise, images and every history key.  (2) With the scale-free stop test and
+    residual balancing on top (read-back only) the run goes to max_iters, and its images and histories
+    are bitwise those recorded on an MI355X from the commit before the table layout was declared in one
+    place (tests/golden/history_run_parent.json; two recordings of that commit were identical)."""
+    import json
+    import os
+    from history_hex import digest, digest_history
+    (x1, h1), (x2, h2) = (every_block_run(pipeline=pl) for pl in (None, False))
+    assert all(np.array_equal(a, b) for a, b in zip(x1, x2))
+    assert set(h1) == set(h2)
+    for k in h1:
+        assert np.array_equal(np.asarray(h1[k]), np.asarray(h2[k]), equal_nan=True), k
+    assert {"psnr_mean", "bound_primal", "consensus_err", "fused_ssim"} <= set(h1)
+    x, h = every_block_run(eps_abs=0.0, eps_rel=1e-9, adapt_rho=True)
+    assert len(h["primal"]) == 3
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "history_run_parent.json")) as f:
+        gold = json.load(f)
+    assert [digest(xi) for xi in x] == gold["images"]
+    got = digest_history(h)
+    assert set(got) == set(gold["history"])
+    for k in got:
+        assert got[k] == gold["history"][k], k
