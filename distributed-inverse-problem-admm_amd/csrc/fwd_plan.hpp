@@ -360,16 +360,20 @@ inline std::vector<FgBlock> fwd_block_order(const FwdPlan& plan, int nch, int cu
 // single round, where the 64-ray plan's equal segment shares keep every XCD on its own row
 // band (512^2, one chunk: 33 us against 35-37 for the clipped plans).
 // forced (ADMM_FWD_PLAN): that plan if the geometry has it; -1: none.
+// A plan with groups but no blocks (a clipped plan of a detector that misses the image: every
+// ray's partial is the zero its slot was filled with) cannot be launched -- a grid of 0 blocks --
+// and counts as a plan the geometry does not have, chosen or forced.
 inline int choose_fwd_plan_index(const int* plan_blocks, const int* plan_n, const double* plan_staged, int nch,
                                  long slots, int forced) {
+  auto has = [&](int pl) { return plan_n[pl] > 0 && plan_blocks[pl] > 0; };
   auto rounds = [&](int pl) { return ((long)plan_blocks[pl] * nch + slots - 1) / slots; };
   int pl = 0;
   for (int q = 1; q < kFwdPlans; ++q) {
-    if (plan_n[q] == 0) continue;
+    if (!has(q)) continue;
     if (rounds(q) < rounds(pl) || (rounds(q) == rounds(pl) && plan_staged[q] < plan_staged[pl])) pl = q;
   }
   if (rounds(pl) == 1 && rounds(0) == 1) pl = 0;
-  if (forced >= 0 && forced < kFwdPlans && plan_n[forced] > 0) pl = forced;
+  if (forced >= 0 && forced < kFwdPlans && has(forced)) pl = forced;
   return pl;
 }
 

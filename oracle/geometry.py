@@ -8,6 +8,10 @@ Geometry restated from /root/reference/block_2_load_odl_data.py:16-65:
   * angles ``uniform_partition(0, pi, a)`` (:51) -> midpoints (t+1/2) pi / a;
     every node spans the full half circle with its own ``a`` angles;
   * detector ``uniform_partition(-w/2, w/2, N)`` (:42-44, :52), w = 2*det_width_factor.
+These are the defaults of :class:`Geometry`; it also takes any uniform detector partition
+(``n_det``, ``det_min``, ``det_max``) and any angle range (``angle_min``, ``angle_max``), the
+free geometry of include/admm_tomo.h, which the functions below read only through ``angles``,
+``det_centers``, ``h_det`` and ``det_min``.
 ODL Parallel2dGeometry defaults: detector axis at angle theta is
 (cos theta, sin theta) and rays run along (-sin theta, cos theta), so detector
 coordinate s sees the line  x cos(theta) + y sin(theta) = s.
@@ -36,10 +40,22 @@ class Geometry:
     N: int
     n_angles: int
     det_width_factor: float = 1.0  # block_2_load_odl_data.py:16,42
+    # The free geometry of include/admm_tomo.h (admm_geom): any uniform detector partition
+    # uniform_partition(det_min, det_max, n_det) and any angle range
+    # uniform_partition(angle_min, angle_max, n_angles).  The defaults are the reference's
+    # (n_det = N, detector [-w/2, w/2], angles over [0, pi]) and give its numbers bit for bit;
+    # with any of n_det / det_min / det_max given, det_width_factor is not read.
+    n_det: int | None = None        # det_pixels = N  (block_2_load_odl_data.py:44)
+    det_min: float | None = None
+    det_max: float | None = None
+    angle_min: float = 0.0
+    angle_max: float = math.pi
 
-    @property
-    def n_det(self) -> int:
-        return self.N  # det_pixels = N  (block_2_load_odl_data.py:44)
+    def __post_init__(self):
+        w = 2.0 * self.det_width_factor
+        for name, default in (("n_det", self.N), ("det_min", -w / 2.0), ("det_max", w / 2.0)):
+            if getattr(self, name) is None:
+                object.__setattr__(self, name, default)
 
     @property
     def h(self) -> float:
@@ -47,20 +63,19 @@ class Geometry:
 
     @property
     def h_det(self) -> float:
-        return 2.0 * self.det_width_factor / self.n_det
+        return (self.det_max - self.det_min) / self.n_det
 
     @property
     def angles(self) -> np.ndarray:
-        # uniform_partition(0, pi, a) midpoints (block_2_load_odl_data.py:51)
+        # uniform_partition(angle_min, angle_max, a) midpoints (block_2_load_odl_data.py:51)
         t = np.arange(self.n_angles, dtype=np.float64)
-        return (t + 0.5) * math.pi / self.n_angles
+        return self.angle_min + (t + 0.5) * (self.angle_max - self.angle_min) / self.n_angles
 
     @property
     def det_centers(self) -> np.ndarray:
-        # uniform_partition(-w/2, w/2, N) midpoints (block_2_load_odl_data.py:52)
-        w = 2.0 * self.det_width_factor
+        # uniform_partition(det_min, det_max, n_det) midpoints (block_2_load_odl_data.py:52)
         k = np.arange(self.n_det, dtype=np.float64)
-        return -w / 2.0 + (k + 0.5) * self.h_det
+        return self.det_min + (k + 0.5) * self.h_det
 
     @property
     def shape(self) -> tuple[int, int]:
@@ -121,6 +136,8 @@ def joseph_matrix(geom: Geometry, dtype=np.float64, angles=None) -> sp.csr_matri
             rows_all.append(row[ok])
             cols_all.append(pix)
             vals_all.append((wt * L)[ok])
+    if not rows_all:  # no ray meets the image (a detector far off it)
+        return sp.csr_matrix((len(tsel) * geom.n_det, N * N), dtype=dtype)
     rows = np.concatenate(rows_all)
     cols = np.concatenate(cols_all)
     vals = np.concatenate(vals_all).astype(dtype)
@@ -145,14 +162,13 @@ def joseph_adjoint_gather(geom: Geometry, y: np.ndarray) -> np.ndarray:
     I = I.ravel().astype(np.float64) - c0
     J = J.ravel().astype(np.float64) - c0
     out = np.zeros(N * N)
-    w_det = 2.0 * geom.det_width_factor
     ratio = geom.h_det / geom.h
     for t, th in enumerate(geom.angles):
         c, s = math.cos(th), math.sin(th)
         alpha = c if abs(c) >= abs(s) else s
         L = geom.h / abs(alpha)
         s_pix = I * c + J * s  # detector coordinate in pixel units
-        kf = (s_pix * geom.h + w_det / 2.0) / geom.h_det - 0.5
+        kf = (s_pix * geom.h - geom.det_min) / geom.h_det - 0.5
         k0 = np.floor(kf)
         f = kf - k0
         k0 = k0.astype(np.int64)

@@ -23,6 +23,7 @@ from collections import namedtuple
 import networkx as nx
 import numpy as np
 
+import free_geom
 from oracle import node_solver as ons
 from oracle import tv as otv
 from oracle.geometry import Geometry, joseph_matrix, shepp_logan
@@ -278,12 +279,20 @@ def ulps(got, want):
 # --------------------------------------------------------------------------------------
 # the x-update cases
 # --------------------------------------------------------------------------------------
-Case = namedtuple("Case", "N V graph tv_iters cg_iters tv_kind a_per mirror fusion derive_z seed")
+# geom: None (the standard geometry of N and a_per) or the id of a free geometry (free_geom.BY_ID)
+Case = namedtuple("Case", "N V graph tv_iters cg_iters tv_kind a_per mirror fusion derive_z seed geom",
+                  defaults=(None,))
 
 
 def _c(N, V, graph, iters, kind, a_per, mirror, edge, seed=1):
     fusion = "weighted" if edge == "weighted" else "midpoint"
     return Case(N, V, graph, iters[0], iters[1], kind, a_per, mirror, fusion, edge == "derived", seed)
+
+
+def _f(geom, V, graph, iters, mirror, edge, seed=1):
+    """A case on the free geometry ``geom`` (isotropic TV)."""
+    g = free_geom.BY_ID[geom]
+    return _c(g.N, V, graph, iters, "iso", g.n_angles, mirror, edge, seed)._replace(geom=geom)
 
 
 # mirror: ADMM_FWD_MIRROR ("1" / "0"; None: an odd angle count, which cannot mirror).
@@ -327,11 +336,35 @@ REUSE_CASES = [
 # a batch with halo rows: rank 0 of 2 of an 8-ring (nodes 0-3, halo images of nodes 4 and 7)
 HALO_CASE = _c(33, 4, "ring", (2, 3), "iso", 12, "1", "derived", seed=2)
 GMIN, UMARGIN = 1e-3, 1e-6  # the conditions' bars
+# x-updates on the free geometries (tests/free_geom.py; test_gpu_free_geom_update.py): n_det != N
+# with mirror mode on and off, an asymmetric detector, the full circle, odd counts, more than one
+# tile and ray chunk, and the geometry the grouped forward kernel does not fit (k_fwd; 1 x 2 inner
+# iterations keep its 256^2 oracle short).  mirror None: the mode the library picks (none of
+# those geometries is mirror-eligible or has a grouped plan).
+FREE_UPDATE_CASES = [
+    _f("wide", 5, "ring", (2, 3), "1", "derived"),
+    _f("wide", 5, "ring", (2, 3), "0", "derived"),
+    _f("coarse", 2, "path", (3, 2), "1", "stored"),
+    _f("shifted", 3, "ring", (2, 3), None, "weighted"),
+    _f("circle", 4, "ring", (1, 5), None, "stored"),
+    _f("odd", 3, "ring", (4, 3), None, "derived"),
+    _f("tiles", 2, "path", (2, 3), None, "stored"),
+    _f("nofit", 2, "path", (1, 2), None, "stored"),
+    _f("nofit", 5, "ring", (1, 2), None, "weighted"),
+]
+# the detector that misses the image (A = 0) under every forced forward plan (test_gpu_free_geom.py)
+MISSED_CASE = _f("missed", 3, "ring", (2, 3), None, "stored")
 
 
 def case_id(c: Case) -> str:
     edge = "weighted" if c.fusion == "weighted" else ("derived" if c.derive_z else "stored")
-    return f"N{c.N}-V{c.V}-{c.graph}-{c.tv_iters}x{c.cg_iters}-{c.tv_kind}-a{c.a_per}m{c.mirror}-{edge}"
+    return ((c.geom + "-") if c.geom else "") + \
+        f"N{c.N}-V{c.V}-{c.graph}-{c.tv_iters}x{c.cg_iters}-{c.tv_kind}-a{c.a_per}m{c.mirror}-{edge}"
+
+
+def case_matrix(c: Case):
+    """The float64 Joseph matrix of a case's geometry."""
+    return joseph_matrix(free_geom.BY_ID[c.geom].oracle() if c.geom else Geometry(c.N, c.a_per))
 
 
 def case_problem(c: Case, dtype: str):
@@ -339,7 +372,7 @@ def case_problem(c: Case, dtype: str):
     from admm_hip.plan import make_plan
     n = c.N * c.N
     plan = make_plan(graph_of(c.graph, c.V), c.V)
-    A = joseph_matrix(Geometry(c.N, c.a_per))
+    A = case_matrix(c)
     b, ph = sinograms(A, c.N, plan.local_nodes, c.seed, dtype)
     W, q_fn = precisions(n, c.V, c.seed)
     prm = ons.NodeParams(rho=RHO, lam=LAM, mu=MU, tv_iters=c.tv_iters, cg_iters=c.cg_iters, tv_kind=c.tv_kind)

@@ -7,6 +7,10 @@ geometry's, as admm_batch_bind halves it).  Checked: the plan rows equal the fix
 the dumped tables are well formed under every plan; fwd_block_order returns permutations that
 deal the XCDs round-robin; the plan choice; and both compilers' programs print the same bytes
 with nothing on stderr.
+
+The free geometries of tests/free_geom.py (n_det != N, detectors not symmetric about 0, other
+angle ranges, one the grouped kernel does not fit) run through the same programs and table
+checks without fixture rows, and a plan without blocks is never chosen or accepted as forced.
 """
 import json
 import math
@@ -15,6 +19,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+import free_geom
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "plan_dump.cpp")
@@ -56,7 +62,12 @@ def programs(tmp_path_factory):
 
 
 def _dump(programs, N, angles, amax, dwf, dtype, what):
-    args = [str(N), str(angles), str(N), (0.0).hex(), float(amax).hex(), (-dwf).hex(), float(dwf).hex(), str(dtype), what]
+    return _dump_geom(programs, N, angles, N, 0.0, amax, -dwf, dwf, dtype, what)
+
+
+def _dump_geom(programs, N, angles, n_det, amin, amax, dmin, dmax, dtype, what):
+    args = [str(N), str(angles), str(n_det), float(amin).hex(), float(amax).hex(), float(dmin).hex(),
+            float(dmax).hex(), str(dtype), what]
     outs = {}
     for name, exe in programs.items():
         r = subprocess.run([exe, *args], capture_output=True, text=True)
@@ -183,3 +194,79 @@ def test_planner_reports_the_geometry_errors(programs):
         r = subprocess.run([exe, *args], capture_output=True, text=True)
         assert r.returncode == 0 and r.stderr == ""
         assert "kf_split" in json.loads(r.stdout)["error"]
+
+
+# ----------------------------------------------------------------------------
+# free geometries (tests/free_geom.py): n_det != N, detectors not symmetric about 0, angle
+# ranges other than [0, pi].  No fixture rows: well-formed tables, identical bytes from both
+# compilers and an empty stderr (sanitizers) are the assertions.
+# ----------------------------------------------------------------------------
+def _blocks(d):
+    return {p["plan"]: len(p["blocks"]) for p in d["plans"]}
+
+
+def _check_choice_has_blocks(d):
+    """Every plan choice -- free, by rounds, forced -- names a plan with blocks; a forced plan
+    the geometry does not have, or has without blocks, falls back to the free choice."""
+    nb = _blocks(d)
+    ch = d["choice"]
+    assert nb.get(ch["one_round"], 0) > 0
+    assert all(nb.get(c, 0) > 0 for c in ch["slots512"])
+    free = ch["forced"][0]
+    assert nb.get(free, 0) > 0 and ch["forced"][7] == free
+    for f in range(6):
+        assert ch["forced"][1 + f] == (f if nb.get(f, 0) > 0 else free), f
+
+
+@pytest.mark.parametrize("dtype", [0, 1], ids=["float32", "float64"])
+@pytest.mark.parametrize("g", free_geom.GEOMS, ids=free_geom.IDS)
+def test_planner_on_free_geometries_is_well_formed(programs, g, dtype):
+    d = _dump_geom(programs, g.N, g.n_angles, g.n_det, g.angle_min, g.angle_max, g.det_min, g.det_max, dtype,
+                   "orders" if g.id in ("wide", "odd") else "tables")
+    assert d["error"] is None
+    _check_tables(d, g.N, g.n_det, g.n_angles)
+    if g.id == "nofit":  # no grouped kernel: the ungrouped k_fwd projects this geometry
+        assert d["fits"] is False and d["plans"] == []
+        return
+    assert d["fits"] is True
+    assert {0, 1} <= set(_blocks(d))  # the mandatory plans
+    if "orders" in d["plans"][0]:
+        _check_orders(d)
+    _check_choice_has_blocks(d)
+    A1 = np.array([a[1] for a in d["fa"]])
+    if g.id in ("circle", "odd", "tiles"):  # past pi/2 .. 3pi/2: descending rays
+        assert (A1 < 0).any() and (A1 > 0).any()
+    if g.id in ("wide", "coarse"):  # mirror-eligible: the half geometry admm_batch_bind plans
+        h = _dump_geom(programs, g.N, g.n_angles // 2, g.n_det, g.angle_min,
+                       g.angle_min + 0.5 * (g.angle_max - g.angle_min), g.det_min, g.det_max, dtype, "tables")
+        assert h["error"] is None and h["fits"] is True
+        _check_tables(h, g.N, g.n_det, g.n_angles // 2)
+        _check_choice_has_blocks(h)
+        assert h["fa"] == d["fa"][: g.n_angles // 2]  # bitwise the full geometry's first half
+
+
+def test_a_plan_without_blocks_is_never_chosen(programs):
+    """A detector that misses the image: the clipped plans 3-5 keep their groups and have no
+    block.  They count as plans the geometry does not have (a launch of 0 blocks is an error):
+    never the free choice, and forced they fall back like a missing plan."""
+    g = free_geom.BY_ID["missed"]
+    for dtype in (0, 1):
+        d = _dump_geom(programs, g.N, g.n_angles, g.n_det, g.angle_min, g.angle_max, g.det_min, g.det_max, dtype,
+                       "tables")
+        nb = _blocks(d)
+        assert all(len(p["groups"]) > 0 for p in d["plans"])
+        assert [nb[p] for p in (3, 4, 5)] == [0, 0, 0] and all(nb[p] > 0 for p in (0, 1, 2))
+        _check_choice_has_blocks(d)
+        ch = d["choice"]
+        assert ch["forced"][4:7] == [ch["forced"][0]] * 3
+
+
+def test_a_detector_that_misses_some_segments(programs):
+    """Detector [1.1, 3.1] at N = 64: its rays meet the image only near the corners, so a clipped
+    plan has fewer blocks than segments x groups and still some; every choice has blocks."""
+    d = _dump_geom(programs, 64, 16, 64, 0.0, math.pi, 1.1, 3.1, 0, "tables")
+    assert d["error"] is None and d["fits"] is True
+    _check_tables(d, 64, 64, 16)
+    p3 = next(p for p in d["plans"] if p["plan"] == 3)
+    assert 0 < len(p3["blocks"]) < d["kFgSeg"] * len(p3["groups"])
+    _check_choice_has_blocks(d)

@@ -4,7 +4,8 @@
 * ``oracle_update`` from the zero state is the node update that
   test_gpu_fullsize.test_fullsize_single_node_update_vs_oracle compares the device with;
 * the conditions under which the random-state x-update cases hold G2 and the shrink tight
-  (state_ref.conditions) hold for every case of test_gpu_state_update.py, on the float64 oracle.
+  (state_ref.conditions) hold for every case of test_gpu_state_update.py and of the free-geometry
+  tests (test_gpu_free_geom_update.py, test_gpu_free_geom.py), on the float64 oracle.
 """
 import networkx as nx
 import numpy as np
@@ -89,7 +90,8 @@ def test_update_cases_cover_every_value():
     assert {(c.N, c.V) for c in sr.REUSE_CASES} == {(33, 3), (33, 8), (65, 3), (65, 8)}
 
 
-@pytest.mark.parametrize("case", sr.UPDATE_CASES + sr.REUSE_CASES + [sr.HALO_CASE], ids=sr.case_id)
+@pytest.mark.parametrize("case", sr.UPDATE_CASES + sr.REUSE_CASES + [sr.HALO_CASE] + sr.FREE_UPDATE_CASES + [sr.MISSED_CASE],
+                         ids=sr.case_id)
 def test_case_conditions_hold_on_the_oracle(case):
     """After the update min |Kx| >= 1e-3 (aniso: min(|gx|, |gy|)) wherever the differences
     exist, so G2 is far from its discontinuity, and no final u lies within 1e-6 of the shrink
