@@ -153,6 +153,11 @@ SYMBOLS = {
     "admm_fuse_deviation": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
                             C.c_void_p],
     "admm_fuse_deviation_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_batch_update_ray_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_batch_refresh_kept": [C.c_void_p, C.c_void_p],
+    "admm_huber_weights": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
+                           C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_huber_weights_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
 }
 
 _lock = threading.Lock()

@@ -48,6 +48,7 @@ from .solver import node_ray_weights
 from ._lib import EDGE_STATS
 from .matrix import MatrixOperator, as_operators
 from .relax import check_relaxation, check_relaxed_run
+from .robust import ROBUST_MATRIX_MSG, applies, check_robust
 from .penalty import (NORM_KEYS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
                       incidences, thresholds)
 from .table import DZ2, G2, IMG, MSE_SINO, QUAD, RA2, RB2, SBRES2, TV
@@ -90,11 +91,28 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              cg_iters=5, tv_kind="iso", group=None, return_tensors=False, timing=None,
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
-             pipeline=None, streams=1, edge_state=None, x_init=None, fuse=None, fuse_out=None,
+             pipeline=None, streams=1, edge_state=None, x_init=None, fuse=None, fuse_out=None, robust=None,
              metrics=None, data_range=None,
              metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
              bound_weight=None, return_feasible=False, ray_weights=None):
-    """``fuse``: None (default), "uniform" or "precision": after every iteration's x-update the network's
+    """``robust``: None (default), a real delta > 0 (inf allowed) or a dict with ``delta`` (required),
+    ``every`` (1: reweight every this many iterations) and ``until`` (None; else after that many iterations
+    the weights stay as they are): the data term of every node becomes the Huber loss
+    sum_r omega_r psi_delta((A x - b)_r), psi_delta(a) = a^2 / 2 for |a| <= delta and delta |a| - delta^2 / 2
+    beyond, minimised by iteratively reweighted rays (admm_hip/robust.py, csrc/robust.hip).
+    After every iteration's last x-update (``inner_tol`` / ``inner_chunks`` solves included) the residual
+    r = A x_i - b_i of every node gives h_r = 1 where |r_r| <= delta, else delta / |r_r|, and -- when
+    (k + 1) % every == 0 and k + 1 <= until -- the next iteration's x-update runs with omega h (omega: the
+    caller's ``ray_weights``, or 1; iteration 0 runs with omega, plain least squares; the precisions W_i,
+    Q_ij stay those of the caller's weights).  Every iteration records ``robust_loss_per_node`` /
+    ``robust_loss_total`` (the weighted Huber value of the iteration's images) and
+    ``robust_outliers_per_node`` / ``robust_outliers_total`` (unmasked rays beyond delta).  ``mse_sino_*``
+    keeps its definition -- the weighted sum under the weights the update ran with -- so ``obj_*`` is the
+    value of the quadratic surrogate, not of the Huber objective.  The values ride in node-table columns
+    and the weights are refreshed on the device, so the pipelined mode stays available.  Geometry
+    operators only; a bool, NaN, delta <= 0, unknown keys and ``every`` < 1 raise ValueError on the host,
+    on every rank alike.  With robust=None nothing changes: no launch, no buffer, no column, no history key.
+    ``fuse``: None (default), "uniform" or "precision": after every iteration's x-update the network's
     images are fused on the GPU into xbar = (sum_i W_i x_i) / (sum_i W_i) per pixel over all graph nodes
     (W = Wi_list; "uniform": W = 1, the plain mean) and the history gains ``consensus_err`` =
     sqrt(sum_i |x_i - xbar|^2) -- unlike ``primal`` independent of the graph and its edge count --,
@@ -217,6 +235,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     tol = check_stop_tolerances(eps_abs, eps_rel)
     check_tolerance_run(tol, edge_state, forced)
     fuse = check_fuse(fuse)
+    robust = check_robust(robust)
     if fuse is None and fuse_out is not None:
         raise ValueError("fuse_out needs fuse='uniform' or 'precision'")
     if fuse_out is not None and not isinstance(fuse_out, dict):
@@ -238,6 +257,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         for g, A in enumerate(A_dense_list):
             if node_ray_weights(ray_weights, [g], A.geom.m) is not None and hasattr(A.geom, "create_ctx"):
                 raise ValueError(CSR_WEIGHTS_MSG)
+    if robust is not None and any(hasattr(A.geom, "create_ctx") for A in A_dense_list):
+        raise ValueError(ROBUST_MATRIX_MSG)
     world, rank = _dist_info(group)
     torch.cuda.set_device(A_dense_list[0].device)
     if snapshot_dir is not None:
@@ -256,6 +277,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         rg.start_from(_initial_images(start, A_dense_list, sinograms, plan.local_nodes, rg.device))
     if metrics:
         rg.enable_metrics(metrics, data_range, metrics_mask)
+    if robust is not None:
+        rg.enable_robust(robust)
     if fuse is not None:
         rg.enable_fuse(fuse, Wi_list)  # (after the metrics: the fused image is scored like the nodes')
     if world > 1:
@@ -304,6 +327,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             rg.score_images()  # x is final for this iteration: the consensus writes z and y only
         if fuse is not None:
             rg.fuse_images()
+        if robust is not None:  # the Huber sums of this iteration's images; the next update's weights
+            rg.reweight(applies(robust, k))
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
         if tol is not None:
             rg.node_norms()  # z, y (w, f) are final for this iteration
@@ -353,7 +378,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         timing["V_total"] = V_total
     if write_params and rank == 0:
         _write_params(snapshot_dir, rho_k, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation,
-                      (rho, adapt, rho_changes) if adapt is not None else None, fuse)
+                      (rho, adapt, rho_changes) if adapt is not None else None, fuse, robust)
     if inspect is not None:
         inspect(rg)
     if fuse is not None and fuse_out is not None:  # the returned images' fusion and spread: after the loop's clock
@@ -470,6 +495,12 @@ class _Recorder:
             for key, val in zip(NORM_KEYS, vals):
                 hist[key].append(val)
             eps = vals[:2]
+        if "robust" in v:  # the weighted Huber value and the outlier count per node
+            loss, cnt = v["robust"][:, 0].copy(), v["robust"][:, 1].copy()
+            hist["robust_loss_per_node"].append(loss)
+            hist["robust_loss_total"].append(float(np.sum(loss)))
+            hist["robust_outliers_per_node"].append(cnt)
+            hist["robust_outliers_total"].append(float(np.sum(cnt)))
         if "fuse" in v:  # |x_i - xbar|^2 per node, then -- in the row of global node 0 only -- the scalars
             dev2 = v["fuse"][:, 0].copy()
             hist["consensus_err"].append(math.sqrt(float(np.sum(dev2))))
@@ -598,7 +629,8 @@ def _snapshot(snapshot_dir, k, rg, N):
             plt.close()
 
 
-def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None, fuse=None):
+def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None, fuse=None,
+                  robust=None):
     """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha; a run with residual
     balancing passes the rho its last iteration ran with and ``balancing`` = (rho_0, the checked
     adapt_rho configuration, the number of changes), which becomes one more line)."""
@@ -623,6 +655,9 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxati
                         f"{cfg['rho_max']}], changes = {changes}\n")
             if fuse is not None:
                 f.write(f"Fused image = {fuse} mean over the nodes\n")
+            if robust is not None:
+                f.write(f"Huber data term: delta = {robust['delta']}, reweighted every = {robust['every']}, "
+                        f"until = {robust['until']}\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")
     except Exception as e:  # pragma: no cover
         print(f"[WARN] Could not save internal params: {e}")

@@ -169,3 +169,21 @@ def transmission_data(sino_clean, I0: float, generator=None):
     counts = torch.poisson(float(I0) * torch.exp(-s.to(torch.float64)), generator=generator)
     b = -torch.log(torch.clamp(counts, min=1.0) / float(I0))
     return b.to(s.dtype), (counts / float(I0)).to(s.dtype)
+
+
+def add_zingers(sino, fraction: float, amplitude: float, generator=None):
+    """Outliers nobody can list in advance (zingers, a flickering bin): a copy of ``sino`` with about
+    ``fraction`` (in [0, 1]) of its rays off by +``amplitude`` or -``amplitude`` (either sign with
+    probability 1/2), and the boolean mask of the rays that were hit.  Returns (sino_out, hit), tensors
+    of ``sino``'s shape and device; ``generator``: a torch.Generator on that device (seeded:
+    repeatable)."""
+    s = torch.as_tensor(sino)
+    if not (0.0 <= fraction <= 1.0):
+        raise ValueError("fraction must be in [0, 1]")
+    if not math.isfinite(amplitude):
+        raise ValueError("amplitude must be finite")
+    u = torch.rand(s.shape, generator=generator, device=s.device, dtype=torch.float64)
+    sign = torch.rand(s.shape, generator=generator, device=s.device, dtype=torch.float64)
+    hit = u < float(fraction)
+    off = torch.where(sign < 0.5, -float(amplitude), float(amplitude)).to(s.dtype)
+    return torch.where(hit, s + off, s), hit

@@ -38,6 +38,7 @@ from .penalty import NORM_KEYS, NORM_STATS, check_tolerance_run
 from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
 from .table import NodeColumns
+from ._lib import ADMM_BATCH_KEEP_X
 
 
 def operator_key(A):
@@ -196,7 +197,8 @@ class RankGroups:
         self.streams_requested = streams
         self.metric_names = ()  # enable_metrics
         self.fuse_mode = None  # enable_fuse
-        # the node table's columns (table.py); enable_metrics and enable_fuse widen it
+        self.robust = None  # enable_robust
+        # the node table's columns (table.py); enable_metrics, enable_robust and enable_fuse widen it
         self.columns = NodeColumns()
         if self.bounds is not None:
             self.columns.add("bounds", BOUND_STATS, lambda nb: [nb.bound_stats], BOUND_KEYS)
@@ -363,6 +365,52 @@ class RankGroups:
         def score(nb):
             nb.metric_cols = nb.scorer.columns(nb.x_local, self.metric_names)
         self._concurrent(score)
+
+    def enable_robust(self, cfg) -> None:
+        """The Huber data term by reweighted rays from now on (robust.check_robust's configuration;
+        ``reweight``).  Every batch gets weights here, at setup -- the caller's, or all-ones, which are
+        bitwise the unweighted batch -- so the weighted launches are recorded once and every later
+        refresh is NodeBatch.update_ray_weights.  Each batch gets the kernel's scratch (robust.HuberWeights)
+        and its projection buffers (one warm-up projection: the operator's scratch is allocated here,
+        not in the loop); the node table gains the block ``robust``: the weighted Huber value and the
+        outlier count per node.  Explicit-matrix operators raise ValueError before any device work."""
+        from .robust import ROBUST_KEYS, ROBUST_MATRIX_MSG, ROBUST_STATS, HuberWeights, check_robust
+        self.robust = check_robust(cfg)
+        self.columns.remove("robust")
+        if self.robust is None:
+            return
+        if any(hasattr(nb.geom, "create_ctx") for nb in self.batches):
+            raise ValueError(ROBUST_MATRIX_MSG)
+        self.columns.add("robust", ROBUST_STATS, lambda nb: [nb.huber.sums], ROBUST_KEYS)
+        for nb in self.batches:
+            nb.robust_base = nb.ray_weights  # omega: the caller's weights, None for 1
+            if nb.ray_weights is None:
+                nb.set_ray_weights(torch.ones(nb.geom.m, dtype=torch.float64))
+            nb.huber = HuberWeights(nb.geom.m, nb.V, nb.b.dtype, nb.dev)
+            nb.robust_xs = torch.zeros((nb.V, nb.geom.n), dtype=nb.b.dtype, device=nb.dev)
+            nb.robust_ax = torch.empty((nb.V, nb.geom.m), dtype=nb.b.dtype, device=nb.dev)
+            nb.project_samples(nb.robust_xs, nb.robust_ax)
+        torch.cuda.synchronize(self.device)
+
+    def reweight(self, apply: bool) -> None:
+        """Per batch, on its stream: the sample-rounded local images projected with the batch's
+        operator, the Huber weights and sums of that residual (``nb.huber.sums``, the block ``robust``),
+        and -- ``apply`` -- omega^eff = omega h pushed into the batch for the next x-update
+        (NodeBatch.update_ray_weights), after which a keep_x batch forms its kept A^T omega (A x - b) again
+        under the new weights (NodeBatch.refresh_kept_start), so that the next update starts as every
+        update of a run with fixed weights does.  Call where ``score_images`` is called: x is final for the
+        iteration.  No host synchronisation."""
+        delta = self.robust["delta"]
+
+        def one(nb):
+            nb.robust_xs.copy_(nb.x_local)
+            nb.project_samples(nb.robust_xs, nb.robust_ax)
+            nb.huber.run(nb.robust_ax, nb.b, nb.robust_base, delta, nb._s())
+            if apply:
+                nb.update_ray_weights(nb.huber.w_out)
+                if nb.cb.flags & ADMM_BATCH_KEEP_X:  # the next update starts as the plain run's does
+                    nb.refresh_kept_start()
+        self._concurrent(one)
 
     def enable_fuse(self, mode, Wi_list=None) -> None:
         """Fuse the network's images from now on (fuse.check_fuse modes; ``fuse_images``): every batch gets

@@ -280,6 +280,37 @@ class NodeBatch:
         _lib.check(self.lib.admm_batch_atb(self.ctx.h, C.c_void_p(self.atb.data_ptr()), C.c_void_p(self._s())),
                    "admm_batch_atb")
 
+    def update_ray_weights(self, t) -> None:
+        """New values for the weights of a batch that has some, from the device tensor ``t`` ([V][m] in
+        the sample dtype, contiguous), on the current stream: the library repacks them into its own
+        buffer (admm_batch_update_ray_weights: no host copy, no synchronisation, nothing re-recorded)
+        and A^T (omega b) is formed again.  The next update is bitwise that of a batch given ``t`` by
+        ``set_ray_weights``.  ``ray_weights`` -- what a re-bind applies again -- stays the caller's."""
+        if self.ray_weights is None:
+            raise ValueError("update_ray_weights needs a batch with ray weights (set_ray_weights first)")
+        if not isinstance(t, torch.Tensor) or t.device != self.b.device or t.dtype != self.b.dtype or \
+                tuple(t.shape) != tuple(self.b.shape) or not t.is_contiguous():
+            raise ValueError(f"weights must be a contiguous {self.b.dtype} {tuple(self.b.shape)} tensor on "
+                             f"{self.b.device}")
+        s = C.c_void_p(self._s())
+        _lib.check(self.lib.admm_batch_update_ray_weights(self.ctx.h, C.c_void_p(t.data_ptr()), s),
+                   "admm_batch_update_ray_weights")
+        _lib.check(self.lib.admm_batch_atb(self.ctx.h, C.c_void_p(self.atb.data_ptr()), s), "admm_batch_atb")
+
+    def refresh_kept_start(self) -> None:
+        """After ``update_ray_weights`` on a ``keep_x`` batch that had completed an update: the kept
+        A^T omega (A x - b) formed again under the new weights (admm_batch_refresh_kept, on the current
+        stream), so that the next update starts from it -- as every update of a run with fixed weights
+        does -- instead of projecting x again."""
+        _lib.check(self.lib.admm_batch_refresh_kept(self.ctx.h, C.c_void_p(self._s())), "admm_batch_refresh_kept")
+
+    def project_samples(self, xs, out) -> None:
+        """``out`` ([V][m]) <- A ``xs`` ([V][n]), both contiguous in the sample dtype, with the batch's
+        own operator context on the current stream (admm_project_fwd: the operator scratch, not the
+        bound batch's)."""
+        _lib.check(self.lib.admm_project_fwd(self.ctx.h, C.c_void_p(xs.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             self.V, C.c_void_p(self._s())), "admm_project_fwd")
+
     def set_precisions(self, qs) -> None:
         """New q_ij for a batch bound with one q slot per incidence (in incidence order): the
         slots are rewritten (q_c of a batch with bounds is not one of them and stays), D = sum_j q_ij

@@ -8,6 +8,7 @@ over the ranks in one collective (exchange.assemble_stats_*) and turned into his
     metrics  one column per requested image metric                    (RankGroups.enable_metrics)
     bounds   the projection's BOUND_STATS sums                        (a run with bounds)
     norms    the stop test's NORM_STATS sums X2, Z2, U2               (RankGroups(stop_norms=True))
+    robust   the Huber value and the outlier count of the ROBUST_STATS sums   (RankGroups.enable_robust)
     fuse     |x_i - xbar|^2, then -- in the row of global node 0 only, zero elsewhere -- the
              FUSE_SCALARS scalars and one column per metric of the fused image (RankGroups.enable_fuse)
 
@@ -26,7 +27,7 @@ from ._lib import EDGE_STATS, NODE_STATS
 MSE_SINO, G2, TV, QUAD, IMG, SBRES2 = range(NODE_STATS)
 RA2, RB2, DZ2 = range(EDGE_STATS)
 
-ORDER = ("core", "metrics", "bounds", "norms", "fuse")
+ORDER = ("core", "metrics", "bounds", "norms", "robust", "fuse")
 
 HISTORY_KEYS = (
     "primal", "dual", "pri_per_node", "dual_per_node", "obj_per_node", "obj_total",

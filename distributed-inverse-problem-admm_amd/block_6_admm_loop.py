@@ -49,6 +49,11 @@ Beyond the reference's surface:
                 fused_psnr / fused_ssim (admm_hip/admm.py, admm_hip/fuse.py)
 * ``fuse_out``  a dict that receives "image" (the fusion of the returned images) and "spread" (their
                 per-pixel weighted standard deviation across nodes) as (N, N) arrays
+* ``robust``    None (default), a Huber threshold delta > 0 or a dict (delta, every, until): the data term
+                becomes the Huber loss, minimised by reweighting the rays from each iteration's residual
+                (h = min(1, delta / |A x - b|) times ``ray_weights``); adds the history keys
+                robust_loss_per_node / robust_loss_total, robust_outliers_per_node /
+                robust_outliers_total; geometry operators only (admm_hip/admm.py, admm_hip/robust.py)
 """
 from __future__ import annotations
 
@@ -74,7 +79,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_acceleration=1, scs_lookback=10, scs_scale=1e-1,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
-                       phantom_true=None, write_params=True, fuse=None, fuse_out=None,
+                       phantom_true=None, write_params=True, fuse=None, fuse_out=None, robust=None,
                        adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
                        bound_weight=None, return_feasible=False, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
@@ -92,7 +97,8 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        chunk_snapshot_dir=scs_snapshot_dir if chunks is not None else None,
                        chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights, bounds=bounds,
                        bound_weight=bound_weight, return_feasible=return_feasible, relaxation=relaxation,
-                       adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel, fuse=fuse, fuse_out=fuse_out)
+                       adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel, fuse=fuse, fuse_out=fuse_out,
+                       robust=robust)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

@@ -58,6 +58,11 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 fused_psnr / fused_ssim (admm_hip/admm.py, admm_hip/fuse.py)
 * ``fuse_out``  a dict that receives "image" (the fusion of the returned images) and "spread" (their
                 per-pixel weighted standard deviation across nodes) as (N, N) arrays
+* ``robust``    None (default), a Huber threshold delta > 0 or a dict (delta, every, until): the data term
+                becomes the Huber loss, minimised by reweighting the rays from each iteration's residual
+                (h = min(1, delta / |A x - b|) times ``ray_weights``); adds the history keys
+                robust_loss_per_node / robust_loss_total, robust_outliers_per_node /
+                robust_outliers_total; geometry operators only (admm_hip/admm.py, admm_hip/robust.py)
 
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
@@ -74,7 +79,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        snapshot_every=None, snapshot_div=10, phantom_true=None,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
-                       max_inner_updates=10, x_init=None, fuse=None, fuse_out=None,
+                       max_inner_updates=10, x_init=None, fuse=None, fuse_out=None, robust=None,
                        metrics=None, data_range=None, metrics_mask=None,
                        adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None,
                        bounds=None, bound_weight=None,
@@ -91,4 +96,4 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights,
                     bounds=bounds, bound_weight=bound_weight, return_feasible=return_feasible,
                     relaxation=relaxation, adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel,
-                    fuse=fuse, fuse_out=fuse_out)
+                    fuse=fuse, fuse_out=fuse_out, robust=robust)

@@ -253,6 +253,9 @@ struct admm_ctx {
   size_t tf_next = 0;
   int tf_kind = 0;  // what the in-solve events bracket: 0 forward taps, 1 back projector (BACK_H)
   bool ats_valid = false;  // ats matches x_ext's local rows
+  // ats was valid until admm_batch_update_ray_weights changed the weights: xs, xsT still hold the last
+  // update's x, so admm_batch_refresh_kept can form A^T s again (any other loss of ats clears it)
+  bool ats_stale = false;
   Buf partH, partS, partD, partE;
   Buf redH;
   int P_back = 0, P_tile = 0, P_fwd = 0, P_edge = 0;
@@ -1249,7 +1252,7 @@ int admm_batch_bind(admm_ctx* C, const admm_batch* batch) {
   if (B.cg_iters > 1 && B.cg_iters <= kMaxCgRing)
     RET(ensure(C->pring, (size_t)(B.cg_iters - 1) * Vp * npix * ds));
   if (B.flags & ADMM_BATCH_KEEP_X) RET(ensure(C->ats, Vp * npix * ds));
-  C->ats_valid = false;
+  C->ats_valid = C->ats_stale = false;
   RET(ensure(C->sino, Vp * m * ds));
   RET(ensure(C->bI, Vp * m * ds));
   RET(ensure(C->r, V * npix * 8));
@@ -1302,7 +1305,7 @@ int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
   HIPCHK(hipDeviceSynchronize());
   if (!w && !C->weighted) return ADMM_OK;
   C->weighted = false;
-  C->ats_valid = false;  // the kept A^T s belongs to the previous weights
+  C->ats_valid = C->ats_stale = false;  // the kept A^T s belongs to the previous weights
   if (w) {
     const int V = C->b.V, m = C->mrays;
     const size_t Vp = (size_t)((V + C->vb - 1) / C->vb) * C->vb;
@@ -1320,6 +1323,78 @@ int admm_batch_set_ray_weights(admm_ctx* C, const void* w, void* stream) {
   }
   RET(record_graphs(C));
   HIPCHK(hipDeviceSynchronize());
+  return ADMM_OK;
+}
+
+// New values for the weights of a batch that has some (robust reweighting): the set
+// call's k_pack launch into the same wS, on `stream`, and nothing else.  The recorded sequences
+// already hold the weighted launches and read wS by its pointer, which does not move: wS is sized by
+// V, m and the dtype of the bound batch (ensure() keeps a buffer that is large enough), and a bind,
+// the only call that changes those, clears `weighted`, so the next weights come through the set call.
+int admm_batch_update_ray_weights(admm_ctx* C, const void* w, void* stream) {
+  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
+  if (C->csr)
+    return fail(ADMM_E_INVALID, "per-ray weights are not supported for explicit-matrix contexts: scale the "
+                                "rows of A and b by sqrt(omega) instead (exact there)");
+  if (!w) return fail(ADMM_E_INVALID, "w is null (admm_batch_set_ray_weights clears the weights)");
+  if (!C->weighted) return fail(ADMM_E_STATE, "the batch has no ray weights: admm_batch_set_ray_weights first");
+  DEVICE_SCOPE(C->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int V = C->b.V, m = C->mrays;
+  RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    using T = typename decltype(tt)::type;
+    constexpr int VB = decltype(vbc)::value;
+    const dim3 grid((m + 255) / 256, (V + VB - 1) / VB);
+    hipLaunchKernelGGL((k_pack<T, VB>), grid, dim3(256), 0, s, (const T*)w, (T*)C->wS.p, m, V);
+    CHECK_LAUNCH();
+    return ADMM_OK;
+  }));
+  C->ats_stale = C->ats_stale || C->ats_valid;  // (what admm_batch_refresh_kept may form again)
+  C->ats_valid = false;  // the kept A^T s belongs to the previous weights
+  return ADMM_OK;
+}
+
+// The kept A^T s of a KEEP_X batch formed again under the weights admm_batch_update_ray_weights gave
+// it: the update's own epilogue launches -- s = omega (A xs - b) from the kept samples xs of the last
+// update's x, then the DIAG back projection into ats -- without the reductions into node_stats (their
+// partials land in the update's scratch, which the next update overwrites).  The next update then
+// starts from k_start_reuse, as in a run whose weights never change; with unchanged weights the
+// launches and their inputs are the epilogue's, so ats is bitwise what the update left.
+int admm_batch_refresh_kept(admm_ctx* C, void* stream) {
+  if (!C || !C->bound) return fail(ADMM_E_STATE, "no batch bound");
+  if (!(C->b.flags & ADMM_BATCH_KEEP_X) || !C->ats_stale)
+    return fail(ADMM_E_STATE, "no kept A^T s to refresh: a KEEP_X batch right after admm_batch_update_ray_weights");
+  DEVICE_SCOPE(C->device);
+  hipStream_t s = (hipStream_t)stream;
+  RET(with_type_vb(C->dtype, C->vb, [&](auto tt, auto vbc) {
+    using T = typename decltype(tt)::type;
+    constexpr int VB = decltype(vbc)::value;
+    const admm_batch& B = C->b;
+    T* sino = (T*)C->sino.p;
+    RET((launch_fwd_batch<T, VB, 1>(C, (T*)C->xs.p, (T*)C->xsT.p, sino, (const T*)B.b, (double*)C->partS.p, B.V, s)));
+    BackArgs<T> a{};
+    a.sino = sino;
+    a.part = (double*)C->partD.p;
+    a.dsum = B.dsum;
+    a.cvec = (double*)C->c.p;
+    a.x = B.x_ext;
+    a.phantom = B.phantom;
+    a.edges = edge_in(B);
+    a.qv = B.q;
+    a.inc_off = B.inc_off;
+    a.inc_edge = B.inc_edge;
+    a.inc_qslot = B.inc_qslot;
+    a.inc_sign = B.inc_sign;
+    a.rho = B.rho;
+    a.lam = B.lam;
+    a.mu = B.mu;
+    a.tv_kind = B.tv_kind;
+    a.evar = B.e;
+    a.out_t = (T*)C->ats.p;
+    return launch_back<T, VB, BACK_DIAG>(C, a, B.V, s);
+  }));
+  C->ats_valid = true;
+  C->ats_stale = false;
   return ADMM_OK;
 }
 
@@ -1345,7 +1420,7 @@ int admm_batch_set_rho(admm_ctx* C, double rho, void* stream) {
     return ADMM_OK;
   }));
   HIPCHK(hipStreamSynchronize(C->cap.s));
-  C->ats_valid = false;  // (one projection more in the next update: the reuse start is not reasoned about)
+  C->ats_valid = C->ats_stale = false;  // (one projection more in the next update: the reuse start is not reasoned about)
   RET(record_graphs(C));
   HIPCHK(hipDeviceSynchronize());
   return ADMM_OK;
@@ -1388,6 +1463,7 @@ int admm_node_update(admm_ctx* C, void* stream) {
     rc = enqueue_update_any(C, s, reuse);
   }
   if (rc == ADMM_OK && keep) C->ats_valid = true;  // this update's DIAG left A^T s of its x
+  C->ats_stale = false;
   return rc;
 }
 
@@ -1402,6 +1478,7 @@ int admm_node_update_rounds(admm_ctx* C, int tv_iters, void* stream) {
   // a round count other than the bound one: enqueued directly (no recorded graph)
   const int rc = enqueue_update_any(C, s, reuse, tv_iters);
   if (rc == ADMM_OK && keep) C->ats_valid = true;
+  C->ats_stale = false;
   return rc;
 }
 

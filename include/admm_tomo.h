@@ -210,6 +210,23 @@ int admm_batch_atb(admm_ctx* ctx, double* atb_out, void* stream);
  * Explicit-matrix contexts: ADMM_E_INVALID (scale the rows of A and b by sqrt(omega) there).
  * Additive: ADMM_ABI_VERSION stays 9. */
 int admm_batch_set_ray_weights(admm_ctx* ctx, const void* w, void* stream);
+/* New values for the weights of a bound batch that already has some (ADMM_E_STATE otherwise;
+ * explicit-matrix contexts: ADMM_E_INVALID): w ([V][m], context dtype, not NULL) is packed into the
+ * library's own buffer by the set call's launch, on `stream`, and the kept A^T s is dropped.  Nothing
+ * else: no synchronisation and no re-recording -- the recorded sequences hold the weighted launches and
+ * read that buffer by a pointer that does not move while the batch stays bound.  Follow it with
+ * admm_batch_atb.  The next admm_node_update is bitwise that of a batch given the same weights by
+ * admm_batch_set_ray_weights.  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_batch_update_ray_weights(admm_ctx* ctx, const void* w, void* stream);
+/* For a batch bound with ADMM_BATCH_KEEP_X whose kept A^T s admm_batch_update_ray_weights has just dropped
+ * (ADMM_E_STATE otherwise): the kept A^T s formed again under the new weights, from the samples of the
+ * last update's x that the library still holds, by that update's own epilogue launches on `stream` -- the
+ * forward projection with the weighted residual and the back projection -- without touching node_stats.
+ * The next admm_node_update then starts from the kept A^T s as it does in a run whose weights never
+ * change, instead of projecting x again; if the new weights equal the old ones bit for bit, so does the
+ * kept A^T s and with it that update.  No synchronisation, nothing re-recorded.  Additive:
+ * ADMM_ABI_VERSION stays 9. */
+int admm_batch_refresh_kept(admm_ctx* ctx, void* stream);
 /* One x-update of every bound node: neighbour gather v_ij = z_ij - y_ij,i
  * (y_ij,i = y for the lower endpoint, -y or y_b for the higher one),
  * fixed-count split-Bregman/CG solve of eq.(1), diagnostics into node_stats.
@@ -485,6 +502,30 @@ int admm_fuse_deviation(const double* x, long long x_stride, const double* mean,
                         double* out, void* stream);
 /* *n_doubles = the doubles of `work` admm_fuse_deviation needs for this n and nimg.  No device work. */
 int admm_fuse_deviation_work(long long n, int nimg, long long* n_doubles);
+
+/* --- the Huber data term by reweighted rays --- */
+
+/* Context-free.  ax, b, w (or NULL: w = 1) and w_out are [nimg][m], contiguous, of the sample type T =
+ * dtype (ADMM_DTYPE_*); w_out is distinct from the inputs; out is [nimg][2] float64.  Per ray, every
+ * line one IEEE operation:
+ *
+ *   r = ax - b (T);  a = |(double)r|;  h64 = a <= delta ? 1.0 : delta / a;  h = (T)h64
+ *   w_out = w ? w * h (T) : h
+ *   psi = a <= delta ? 0.5 * (a * a) : delta * a - hd,   hd = 0.5 * (delta * delta) formed on the host
+ *   out[v][0] = sum_r (double)w psi,   out[v][1] = the number of rays with w != 0 and a > delta
+ *
+ * the Huber weights of the residual and the weighted Huber value of image v.  A ray with w == 0 is masked:
+ * w_out = 0, its term is +0 whatever ax and b hold, and it is not counted.  delta > 0, not NaN; +inf is
+ * allowed: every h = 1 and w_out is w (or 1) bitwise.  A NaN residual propagates.  The sums are per-block
+ * partials in fixed slots of `work` (admm_huber_weights_work doubles, caller-owned), then one fixed-order
+ * sum per image, as admm_node_norms does: an image's results depend neither on nimg nor on its place in
+ * the batch.  No atomics.  Allocates nothing; arguments are checked before any HIP call (ADMM_E_INVALID);
+ * asynchronous on `stream` (current device).  Reads 2 (3 with w) and writes 1 sample per ray.
+ * Additive: ADMM_ABI_VERSION stays 9. */
+int admm_huber_weights(const void* ax, const void* b, const void* w, void* w_out, int dtype, long long m, int nimg,
+                       double delta, double* work, double* out, void* stream);
+/* *n_doubles = the doubles of `work` admm_huber_weights needs for this m and nimg.  No device work. */
+int admm_huber_weights_work(long long m, int nimg, long long* n_doubles);
 
 #ifdef __cplusplus
 }
