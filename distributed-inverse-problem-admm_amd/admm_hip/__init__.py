@@ -10,8 +10,8 @@ from ._lib import AdmmError, AdmmLibraryError  # noqa: F401
 from .fbp import FILTERS, fbp, filter_taps, ramp_filter  # noqa: F401
 from .metrics import image_metrics, psnr, ssim  # noqa: F401
 from .fuse import Fuser, check_fuse, fuse_images  # noqa: F401
-from .robust import check_robust, huber_weights  # noqa: F401
+from .robust import check_robust, huber_weights, ray_quantile  # noqa: F401
 
 __all__ = ["ParallelBeamGeometry", "RayTransform", "split_angles", "AdmmError", "AdmmLibraryError",
            "FILTERS", "fbp", "filter_taps", "ramp_filter", "image_metrics", "psnr", "ssim", "Fuser", "check_fuse",
-           "fuse_images", "check_robust", "huber_weights"]
+           "fuse_images", "check_robust", "huber_weights", "ray_quantile"]

@@ -158,6 +158,11 @@ SYMBOLS = {
     "admm_huber_weights": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
     "admm_huber_weights_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+    "admm_huber_weights_dev": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
+                               C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_ray_quantile": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double,
+                          C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "admm_ray_quantile_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
 }
 
 _lock = threading.Lock()

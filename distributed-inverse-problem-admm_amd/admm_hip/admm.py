@@ -48,7 +48,7 @@ from .solver import node_ray_weights
 from ._lib import EDGE_STATS
 from .matrix import MatrixOperator, as_operators
 from .relax import check_relaxation, check_relaxed_run
-from .robust import ROBUST_MATRIX_MSG, applies, check_robust
+from .robust import ROBUST_MATRIX_MSG, applies, check_robust, estimates
 from .penalty import (NORM_KEYS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
                       incidences, thresholds)
 from .table import DZ2, G2, IMG, MSE_SINO, QUAD, RA2, RB2, SBRES2, TV
@@ -112,6 +112,16 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     and the weights are refreshed on the device, so the pipelined mode stays available.  Geometry
     operators only; a bool, NaN, delta <= 0, unknown keys and ``every`` < 1 raise ValueError on the host,
     on every rank alike.  With robust=None nothing changes: no launch, no buffer, no column, no history key.
+    The self-scaling form: a dict with ``scale`` (a finite real > 0; no default) in place of
+    ``delta``, and optionally ``quantile`` (0.5), ``delta_min`` (0.0) and ``consistency`` (1.4826): every
+    iteration each node's threshold is delta_i = max(scale * consistency * a_k, delta_min), a_k the
+    floor(quantile (cnt - 1))-th smallest |A x_i - b_i| among the cnt rays the caller's ``ray_weights`` do not
+    mask (the lower median) -- an exact order statistic found on the device (csrc/scale.hip) and read by the
+    Huber kernel from device memory, no host synchronisation; a zero or non-finite estimate gives
+    delta_i = inf (least squares), never 0.  The estimate is refreshed while k + 1 <= until (always at
+    k = 0), then kept; until it is frozen a moving delta gives up the fixed-delta descent guarantee of
+    majorise-minimise.  The history gains ``robust_delta_per_node`` (the thresholds formed from the
+    iteration's images); loss and outliers are reported at the threshold in force.
     ``fuse``: None (default), "uniform" or "precision": after every iteration's x-update the network's
     images are fused on the GPU into xbar = (sum_i W_i x_i) / (sum_i W_i) per pixel over all graph nodes
     (W = Wi_list; "uniform": W = 1, the plain mean) and the history gains ``consensus_err`` =
@@ -328,7 +338,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         if fuse is not None:
             rg.fuse_images()
         if robust is not None:  # the Huber sums of this iteration's images; the next update's weights
-            rg.reweight(applies(robust, k))
+            rg.reweight(applies(robust, k), estimates(robust, k))
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
         if tol is not None:
             rg.node_norms()  # z, y (w, f) are final for this iteration
@@ -501,6 +511,8 @@ class _Recorder:
             hist["robust_loss_total"].append(float(np.sum(loss)))
             hist["robust_outliers_per_node"].append(cnt)
             hist["robust_outliers_total"].append(float(np.sum(cnt)))
+            if v["robust"].shape[1] > 2:  # the scale form: the threshold formed from this iteration's images
+                hist["robust_delta_per_node"].append(v["robust"][:, 2].copy())
         if "fuse" in v:  # |x_i - xbar|^2 per node, then -- in the row of global node 0 only -- the scalars
             dev2 = v["fuse"][:, 0].copy()
             hist["consensus_err"].append(math.sqrt(float(np.sum(dev2))))
@@ -655,7 +667,12 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxati
                         f"{cfg['rho_max']}], changes = {changes}\n")
             if fuse is not None:
                 f.write(f"Fused image = {fuse} mean over the nodes\n")
-            if robust is not None:
+            if robust is not None and "scale" in robust:
+                f.write(f"Huber data term: delta = scale x consistency x quantile of |A x - b| per node, scale = "
+                        f"{robust['scale']}, consistency = {robust['consistency']}, quantile = "
+                        f"{robust['quantile']}, delta_min = {robust['delta_min']}, reweighted every = "
+                        f"{robust['every']}, until = {robust['until']}\n")
+            elif robust is not None:
                 f.write(f"Huber data term: delta = {robust['delta']}, reweighted every = {robust['every']}, "
                         f"until = {robust['until']}\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")

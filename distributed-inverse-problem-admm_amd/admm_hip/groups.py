@@ -373,39 +373,61 @@ class RankGroups:
         refresh is NodeBatch.update_ray_weights.  Each batch gets the kernel's scratch (robust.HuberWeights)
         and its projection buffers (one warm-up projection: the operator's scratch is allocated here,
         not in the loop); the node table gains the block ``robust``: the weighted Huber value and the
-        outlier count per node.  Explicit-matrix operators raise ValueError before any device work."""
-        from .robust import ROBUST_KEYS, ROBUST_MATRIX_MSG, ROBUST_STATS, HuberWeights, check_robust
+        outlier count per node.  The scale form (``scale`` in the configuration) also gives each batch a
+        robust.RayQuantile, and the block a third column: the threshold in force, read from the quantile's
+        output without a launch.  Explicit-matrix operators raise ValueError before any device work."""
+        from .robust import (ROBUST_KEYS, ROBUST_MATRIX_MSG, ROBUST_SCALE_KEYS, ROBUST_SCALE_STATS, ROBUST_STATS,
+                             HuberWeights, RayQuantile, check_robust, scale_factor)
         self.robust = check_robust(cfg)
         self.columns.remove("robust")
         if self.robust is None:
             return
         if any(hasattr(nb.geom, "create_ctx") for nb in self.batches):
             raise ValueError(ROBUST_MATRIX_MSG)
-        self.columns.add("robust", ROBUST_STATS, lambda nb: [nb.huber.sums], ROBUST_KEYS)
+        scaled = "scale" in self.robust
+        if scaled:
+            self.robust_c = scale_factor(self.robust)  # formed once
+            self.columns.add("robust", ROBUST_SCALE_STATS, lambda nb: [nb.huber.sums, nb.quant.out[:, 0:1]],
+                             ROBUST_SCALE_KEYS)
+        else:
+            self.columns.add("robust", ROBUST_STATS, lambda nb: [nb.huber.sums], ROBUST_KEYS)
         for nb in self.batches:
             nb.robust_base = nb.ray_weights  # omega: the caller's weights, None for 1
             if nb.ray_weights is None:
                 nb.set_ray_weights(torch.ones(nb.geom.m, dtype=torch.float64))
             nb.huber = HuberWeights(nb.geom.m, nb.V, nb.b.dtype, nb.dev)
+            if scaled:
+                nb.quant = RayQuantile(nb.geom.m, nb.V, nb.b.dtype, nb.dev)
             nb.robust_xs = torch.zeros((nb.V, nb.geom.n), dtype=nb.b.dtype, device=nb.dev)
             nb.robust_ax = torch.empty((nb.V, nb.geom.m), dtype=nb.b.dtype, device=nb.dev)
             nb.project_samples(nb.robust_xs, nb.robust_ax)
         torch.cuda.synchronize(self.device)
 
-    def reweight(self, apply: bool) -> None:
+    def reweight(self, apply: bool, estimate: bool = True) -> None:
         """Per batch, on its stream: the sample-rounded local images projected with the batch's
         operator, the Huber weights and sums of that residual (``nb.huber.sums``, the block ``robust``),
         and -- ``apply`` -- omega^eff = omega h pushed into the batch for the next x-update
         (NodeBatch.update_ray_weights), after which a keep_x batch forms its kept A^T omega (A x - b) again
         under the new weights (NodeBatch.refresh_kept_start), so that the next update starts as every
-        update of a run with fixed weights does.  Call where ``score_images`` is called: x is final for the
-        iteration.  No host synchronisation."""
-        delta = self.robust["delta"]
+        update of a run with fixed weights does.  The scale form: between the projection and the Huber
+        kernel -- ``estimate`` (robust.estimates) -- each node's threshold is formed again from this residual
+        (admm_ray_quantile; masked are the caller's zeros, never the moving weights), and the Huber kernel
+        reads the thresholds in place from the device (admm_huber_weights_dev); without ``estimate`` they
+        stay at their last values.  Call where ``score_images`` is called: x is final for the iteration.
+        No host synchronisation."""
+        cfg = self.robust
+        scaled = "scale" in cfg
 
         def one(nb):
             nb.robust_xs.copy_(nb.x_local)
             nb.project_samples(nb.robust_xs, nb.robust_ax)
-            nb.huber.run(nb.robust_ax, nb.b, nb.robust_base, delta, nb._s())
+            if scaled:
+                if estimate:
+                    nb.quant.run(nb.robust_ax, nb.b, nb.robust_base, cfg["quantile"], self.robust_c, cfg["delta_min"],
+                                 nb._s())
+                nb.huber.run(nb.robust_ax, nb.b, nb.robust_base, nb.quant.delta, nb._s())
+            else:
+                nb.huber.run(nb.robust_ax, nb.b, nb.robust_base, cfg["delta"], nb._s())
             if apply:
                 nb.update_ray_weights(nb.huber.w_out)
                 if nb.cb.flags & ADMM_BATCH_KEEP_X:  # the next update starts as the plain run's does

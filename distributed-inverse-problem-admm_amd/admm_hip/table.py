@@ -8,7 +8,8 @@ over the ranks in one collective (exchange.assemble_stats_*) and turned into his
     metrics  one column per requested image metric                    (RankGroups.enable_metrics)
     bounds   the projection's BOUND_STATS sums                        (a run with bounds)
     norms    the stop test's NORM_STATS sums X2, Z2, U2               (RankGroups(stop_norms=True))
-    robust   the Huber value and the outlier count of the ROBUST_STATS sums   (RankGroups.enable_robust)
+    robust   the Huber value and the outlier count of the ROBUST_STATS sums   (RankGroups.enable_robust);
+             the scale form adds the threshold in force (ROBUST_SCALE_STATS columns)
     fuse     |x_i - xbar|^2, then -- in the row of global node 0 only, zero elsewhere -- the
              FUSE_SCALARS scalars and one column per metric of the fused image (RankGroups.enable_fuse)
 

@@ -49,7 +49,8 @@ Beyond the reference's surface:
                 fused_psnr / fused_ssim (admm_hip/admm.py, admm_hip/fuse.py)
 * ``fuse_out``  a dict that receives "image" (the fusion of the returned images) and "spread" (their
                 per-pixel weighted standard deviation across nodes) as (N, N) arrays
-* ``robust``    None (default), a Huber threshold delta > 0 or a dict (delta, every, until): the data term
+* ``robust``    None (default), a Huber threshold delta > 0 or a dict (delta or scale, every, until; scale:
+                delta_i = scale * 1.4826 * median|A x_i - b_i| per node, found on the GPU): the data term
                 becomes the Huber loss, minimised by reweighting the rays from each iteration's residual
                 (h = min(1, delta / |A x - b|) times ``ray_weights``); adds the history keys
                 robust_loss_per_node / robust_loss_total, robust_outliers_per_node /

@@ -48,13 +48,19 @@ int check_shape(long long m, int nimg) {
 
 namespace admm {
 
-template <typename T>
+// kDev: the image's threshold is delta_dev[v * delta_stride] and hd is formed here, by the host's expression
+template <typename T, bool kDev>
 __global__ __launch_bounds__(kThreads) void k_huber_weights(const T* __restrict__ ax, const T* __restrict__ b,
                                                             const T* __restrict__ w, T* __restrict__ w_out,
                                                             long long m, double delta, double hd,
-                                                            double* __restrict__ work) {
+                                                            const double* __restrict__ delta_dev,
+                                                            long long delta_stride, double* __restrict__ work) {
   __shared__ double red[kSums][kThreads / 64];
   const size_t v = blockIdx.y;
+  if (kDev) {
+    delta = delta_dev[v * (size_t)delta_stride];
+    hd = 0.5 * (delta * delta);
+  }
   const size_t row = v * (size_t)m;
   const long long base = (long long)blockIdx.x * kBlockPix;
   double acc[kSums] = {0.0, 0.0};
@@ -98,6 +104,44 @@ __global__ __launch_bounds__(kThreads) void k_huber_weights(const T* __restrict_
 
 }  // namespace admm
 
+namespace {
+
+// the checks and the two launches both entry points share; delta_dev == nullptr: the host's delta
+int huber_launch(const void* ax, const void* b, const void* w, void* w_out, int dtype, long long m, int nimg,
+                 double delta, const double* delta_dev, long long delta_stride, double* work, double* out,
+                 void* stream) {
+  if (!ax) return fail(ADMM_E_INVALID, "ax is null");
+  if (!b) return fail(ADMM_E_INVALID, "b is null");
+  if (!w_out) return fail(ADMM_E_INVALID, "w_out is null");
+  if (!work) return fail(ADMM_E_INVALID, "work is null");
+  if (!out) return fail(ADMM_E_INVALID, "out is null");
+  if (w_out == ax || w_out == b || w_out == w) return fail(ADMM_E_INVALID, "w_out must be distinct from ax, b and w");
+  if (dtype != ADMM_DTYPE_F32 && dtype != ADMM_DTYPE_F64)
+    return fail(ADMM_E_INVALID, "dtype must be ADMM_DTYPE_F32 or ADMM_DTYPE_F64");
+  if (!delta_dev && (std::isnan(delta) || !(delta > 0.0)))
+    return fail(ADMM_E_INVALID, "delta must be > 0 (+inf allowed), not NaN");
+  if (int rc = check_shape(m, nimg)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const long long P = blocks_of(m);
+  const double hd = 0.5 * (delta * delta);
+  const dim3 grid((unsigned)P, (unsigned)nimg);
+#define ADMM_HUBER_LAUNCH(T, DEV)                                                                             \
+  hipLaunchKernelGGL((k_huber_weights<T, DEV>), grid, dim3(kThreads), 0, s, (const T*)ax, (const T*)b,        \
+                     (const T*)w, (T*)w_out, m, delta, hd, delta_dev, delta_stride, work)
+  if (dtype == ADMM_DTYPE_F64) {
+    if (delta_dev) ADMM_HUBER_LAUNCH(double, true); else ADMM_HUBER_LAUNCH(double, false);
+  } else {
+    if (delta_dev) ADMM_HUBER_LAUNCH(float, true); else ADMM_HUBER_LAUNCH(float, false);
+  }
+#undef ADMM_HUBER_LAUNCH
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_row_sums<kSums>, dim3((unsigned)nimg), dim3(kThreads), 0, s, (const double*)work, P, 0, out);
+  HIP_TRY(hipGetLastError());
+  return ADMM_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int admm_huber_weights_work(long long m, int nimg, long long* n_doubles) {
@@ -109,30 +153,17 @@ int admm_huber_weights_work(long long m, int nimg, long long* n_doubles) {
 
 int admm_huber_weights(const void* ax, const void* b, const void* w, void* w_out, int dtype, long long m, int nimg,
                        double delta, double* work, double* out, void* stream) {
-  if (!ax) return fail(ADMM_E_INVALID, "ax is null");
-  if (!b) return fail(ADMM_E_INVALID, "b is null");
-  if (!w_out) return fail(ADMM_E_INVALID, "w_out is null");
-  if (!work) return fail(ADMM_E_INVALID, "work is null");
-  if (!out) return fail(ADMM_E_INVALID, "out is null");
-  if (w_out == ax || w_out == b || w_out == w) return fail(ADMM_E_INVALID, "w_out must be distinct from ax, b and w");
-  if (dtype != ADMM_DTYPE_F32 && dtype != ADMM_DTYPE_F64)
-    return fail(ADMM_E_INVALID, "dtype must be ADMM_DTYPE_F32 or ADMM_DTYPE_F64");
-  if (std::isnan(delta) || !(delta > 0.0)) return fail(ADMM_E_INVALID, "delta must be > 0 (+inf allowed), not NaN");
-  if (int rc = check_shape(m, nimg)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const long long P = blocks_of(m);
-  const double hd = 0.5 * (delta * delta);
-  const dim3 grid((unsigned)P, (unsigned)nimg);
-  if (dtype == ADMM_DTYPE_F64)
-    hipLaunchKernelGGL(k_huber_weights<double>, grid, dim3(kThreads), 0, s, (const double*)ax, (const double*)b,
-                       (const double*)w, (double*)w_out, m, delta, hd, work);
-  else
-    hipLaunchKernelGGL(k_huber_weights<float>, grid, dim3(kThreads), 0, s, (const float*)ax, (const float*)b,
-                       (const float*)w, (float*)w_out, m, delta, hd, work);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_row_sums<kSums>, dim3((unsigned)nimg), dim3(kThreads), 0, s, (const double*)work, P, 0, out);
-  HIP_TRY(hipGetLastError());
-  return ADMM_OK;
+  return huber_launch(ax, b, w, w_out, dtype, m, nimg, delta, nullptr, 0, work, out, stream);
+}
+
+int admm_huber_weights_dev(const void* ax, const void* b, const void* w, void* w_out, int dtype, long long m,
+                           int nimg, const double* delta, long long delta_stride, double* work, double* out,
+                           void* stream) {
+  if (!delta) return fail(ADMM_E_INVALID, "delta is null");
+  if (delta_stride < 1) return fail(ADMM_E_INVALID, "delta_stride must be >= 1");
+  if (delta == out || (const void*)delta == w_out)
+    return fail(ADMM_E_INVALID, "delta must be distinct from out and w_out");
+  return huber_launch(ax, b, w, w_out, dtype, m, nimg, 1.0, delta, delta_stride, work, out, stream);
 }
 
 }  // extern "C"

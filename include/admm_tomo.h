@@ -526,6 +526,50 @@ int admm_huber_weights(const void* ax, const void* b, const void* w, void* w_out
                        double delta, double* work, double* out, void* stream);
 /* *n_doubles = the doubles of `work` admm_huber_weights needs for this m and nimg.  No device work. */
 int admm_huber_weights_work(long long m, int nimg, long long* n_doubles);
+/* admm_huber_weights with the threshold of image v read from device memory: delta_v = delta[v * delta_stride]
+ * (float64; delta_stride >= 1 doubles, 3 reads admm_ray_quantile's out in place) and hd = 0.5 * (delta_v *
+ * delta_v) formed on the device -- the same single IEEE operations, one kernel text -- so with delta[v] == d
+ * for every v, w_out and out are bitwise those of admm_huber_weights(..., d, ...).  The host never reads
+ * delta, so a NaN or non-positive delta[v] cannot be reported: it is the caller's precondition
+ * (admm_ray_quantile never writes one).  `work` as admm_huber_weights_work says. */
+int admm_huber_weights_dev(const void* ax, const void* b, const void* w, void* w_out, int dtype, long long m,
+                           int nimg, const double* delta, long long delta_stride, double* work, double* out,
+                           void* stream);
+
+/* --- the self-scaling Huber threshold: an exact quantile of |ax - b| --- */
+
+/* Context-free.  ax, b, w (or NULL) are [nimg][m], contiguous, of the sample type T = dtype; out is
+ * [nimg][3] float64.  Per image v:
+ *
+ *   r   = ax - b (T);  a = |r| (T);  a ray with w != NULL and w == 0 is masked and takes no part, whatever
+ *         ax and b hold (NaN included)
+ *   cnt = the number of unmasked rays
+ *   the keys ordered as np.sort(np.abs(r)) orders them: -0 counts as +0, +inf after every finite value,
+ *         NaN after +inf
+ *   k   = (long long)floor(q * (double)(cnt - 1))      one multiply, then the floor; q in [0, 1]
+ *   a_k = the k-th smallest key, counted from 0        (one ray's value: never interpolated, never a sum)
+ *   t   = c * (double)a_k                              one multiply
+ *   delta_v = +inf if cnt == 0 or t is not a finite number > 0, else t >= floor ? t : floor
+ *   out[v] = { delta_v, (double)a_k (0 when cnt == 0), (double)cnt }
+ *
+ * q = 0.5 is the lower median, 0 the minimum, 1 the maximum; c > 0 (1.4826 * scale for a Gaussian scale
+ * estimate), floor >= 0 (+inf allowed: every delta_v = +inf), neither NaN.  A zero estimate (more than half
+ * the rays with exactly zero residual) says nothing about the noise: the fallback is least squares
+ * (+inf), never a zero threshold.  delta_v is never NaN and never <= 0.  An a_k that is NaN is written as
+ * the quiet NaN of float64.
+ *
+ * One block of 1024 threads per image: a most-significant-first radix select on the bit pattern of |r|
+ * (non-negative IEEE values order as unsigned integers), 11 + 10 + 10 bits for float32, 11 + 11 + 11 + 10 +
+ * 10 + 10 for float64, each pass counting into an LDS histogram with integer atomics -- exact in any order,
+ * so an image's three outputs depend on its rays alone: not on nimg, its place in the batch, or the
+ * stream.  No floating-point atomic, no sum of samples.  m in [1, 2^32 - 1], nimg in [1, 65535].  `work`
+ * is not used (admm_ray_quantile_work reports 0 bytes; NULL is accepted).  Allocates nothing; arguments are
+ * checked before any HIP call (ADMM_E_INVALID); asynchronous on `stream`.  Reads 2 (3 with w) samples per
+ * ray and pass.  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_ray_quantile(const void* ax, const void* b, const void* w, int dtype, long long m, int nimg, double q,
+                      double c, double floor, void* work, double* out, void* stream);
+/* *n_bytes = the bytes of `work` admm_ray_quantile needs for this m and nimg (0).  No device work. */
+int admm_ray_quantile_work(long long m, int nimg, long long* n_bytes);
 
 #ifdef __cplusplus
 }
