@@ -11,6 +11,7 @@ from .fbp import FILTERS, fbp, filter_taps, ramp_filter  # noqa: F401
 from .metrics import image_metrics, psnr, ssim  # noqa: F401
 from .fuse import Fuser, check_fuse, fuse_images  # noqa: F401
 from .robust import check_robust, huber_weights, ray_quantile  # noqa: F401
+from . import links  # noqa: F401  (links.edge_list, links.schedule)
 
 __all__ = ["ParallelBeamGeometry", "RayTransform", "split_angles", "AdmmError", "AdmmLibraryError",
            "FILTERS", "fbp", "filter_taps", "ramp_filter", "image_metrics", "psnr", "ssim", "Fuser", "check_fuse",

@@ -139,6 +139,10 @@ SYMBOLS = {
     "admm_bound_project_relaxed": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                    C.c_void_p, C.c_double, C.c_double, C.c_longlong, C.c_int, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p],
+    "admm_consensus_gated": [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p],
+    "admm_consensus_gated_work": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
     "admm_batch_set_rho": [C.c_void_p, C.c_double, C.c_void_p],
     "admm_node_norms": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -47,6 +47,7 @@ from .groups import RankGroups
 from .solver import node_ray_weights
 from ._lib import EDGE_STATS
 from .matrix import MatrixOperator, as_operators
+from .links import check_links, check_links_run, describe, link_age_max, links_up, schedule
 from .relax import check_relaxation, check_relaxed_run
 from .robust import ROBUST_MATRIX_MSG, applies, check_robust, estimates
 from .penalty import (NORM_KEYS, balance, check_adapt_rho, check_stop_tolerances, check_tolerance_run,
@@ -92,10 +93,36 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
              write_params=True, fusion="midpoint", inner_tol=None, max_inner_updates=10,
              inner_chunks=None, chunk_snapshot_dir=None, chunk_save_every=1, inspect=None,
              pipeline=None, streams=1, edge_state=None, x_init=None, fuse=None, fuse_out=None, robust=None,
-             metrics=None, data_range=None,
+             links=None, metrics=None, data_range=None,
              metrics_mask=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
              bound_weight=None, return_feasible=False, ray_weights=None):
-    """``robust``: None (default), a real delta > 0 (inf allowed) or a dict with ``delta`` (required),
+    """``links``: None (default: every edge of G updates in every iteration), a real p in (0, 1], a dict or a
+    bool array: unreliable links (admm_hip/links.py, csrc/links.hip).  At iteration k every
+    edge is up or down.  An up edge performs exactly today's z / y update (relaxed with ``relaxation``, the
+    weighted form with fusion="weighted"); a down edge keeps its y, z (and y_b) bit for bit, both endpoints
+    go on with the last (z, y) they hold, and its three sums are |x_a - z|^2, |x_b - z|^2 -- the true
+    disagreement with the last agreed z -- and 0.  Every node runs its x-update every iteration; the
+    constraint slot of a run with ``bounds`` is node-local and always updated; ``primal``, ``dual``, the
+    per-node arrays, the stop tests, ``adapt_rho`` and the stop norms keep their definitions and read the same
+    tables; a change of rho rescales the scaled duals of down edges too.  p: every edge is up independently
+    with probability p in every iteration (seed 0; 1.0 is None).  A dict with any of ``p`` (1.0), ``seed``
+    (0), ``max_age`` (None or an int >= 1: an edge that has been down that many iterations in a row is forced
+    up, the bounded-delay model) and ``outages`` (a list of (a, b, k0, k1): edge {a, b} is down for
+    k0 <= k < k1, k1=None for good), applied in that order -- an outage wins --; a dict that leaves every
+    edge up in every iteration is None.  A bool array (rows >= max_iters, E) is used as it is, columns in the
+    run's edge order (``admm_hip.links.edge_list(G)``).  The random table is
+    ``np.random.default_rng([seed, 0x4C4E4B53]).random((max_iters, E)) < p`` (``admm_hip.links.schedule``
+    returns the table of any value), the same on every rank.  The gates live on the device (one byte per
+    edge and iteration, uploaded once), so the pipelined mode stays available.  The history gains
+    ``links_up`` (up edges per iteration) and ``link_age_max`` (after each iteration, the largest number of
+    iterations since an edge's last update), host arithmetic on the table.  Randomised edge activation
+    converges almost surely to the same fixed point if every edge is up with positive probability (Iutzeler et
+    al., CDC 2013; stated for exact node solves); expect about 1 / p times the iterations.  A bool, NaN,
+    p <= 0 or p > 1, unknown keys, max_age < 1, an outage that names a non-edge or has k1 <= k0, and an array
+    of the wrong width or with too few rows raise ValueError on the host, on every rank alike.  Needs stored
+    z (ValueError with derived z, forced or chosen by the HBM rule: a derived z has no per-edge age).  With
+    links=None nothing changes: no launch, no buffer, no history key.
+    ``robust``: None (default), a real delta > 0 (inf allowed) or a dict with ``delta`` (required),
     ``every`` (1: reweight every this many iterations) and ``until`` (None; else after that many iterations
     the weights stay as they are): the data term of every node becomes the Huber loss
     sum_r omega_r psi_delta((A x - b)_r), psi_delta(a) = a^2 / 2 for |a| <= delta and delta |a| - delta^2 / 2
@@ -241,6 +268,13 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         raise ValueError("return_feasible needs bounds=(lo, hi)")
     relaxation = check_relaxation(relaxation)
     check_relaxed_run(relaxation, edge_state, forced)
+    links = check_links(links)
+    link_table = None
+    if links is not None:
+        link_table = schedule(G, max_iters, links)  # (the outages' edges and an array's shape are checked here)
+        if not isinstance(links, np.ndarray) and bool(link_table.all()):
+            links = link_table = None  # every edge up in every iteration: the run without the keyword
+    check_links_run(links, edge_state, forced)
     adapt = check_adapt_rho(adapt_rho, rho)
     tol = check_stop_tolerances(eps_abs, eps_rel)
     check_tolerance_run(tol, edge_state, forced)
@@ -280,7 +314,7 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
                     keep_x=inner_tol is None, group=group, streams=streams,  # this loop never writes x itself
                     derive_z=None if edge_state is None else {"stored": False, "derived": True}[edge_state],
                     ray_weights=ray_weights, bounds=bounds, bound_weight=bound_weight if bounds is not None else None,
-                    relaxation=relaxation, stop_norms=tol is not None)
+                    relaxation=relaxation, stop_norms=tol is not None, links=link_table)
     # (masked re-solves of the tolerance mode restore x rows, so that mode re-projects x)
     plan = rg.plan
     if start is not None:
@@ -339,6 +373,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
             rg.fuse_images()
         if robust is not None:  # the Huber sums of this iteration's images; the next update's weights
             rg.reweight(applies(robust, k), estimates(robust, k))
+        if link_table is not None:
+            rg.set_link_row(k)  # this iteration's gates: a row of the device table, no host synchronisation
         rg.exchange_consensus()  # (rank-internal edges under the halo exchange)
         if tol is not None:
             rg.node_norms()  # z, y (w, f) are final for this iteration
@@ -381,6 +417,9 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
     if pipelined and dev_hist is not None and iters_done > flushed:
         flushed = _flush_pipelined(record, dev_hist, flushed, iters_done, rho, verbose and rank == 0)
     torch.cuda.synchronize()
+    if link_table is not None:  # host arithmetic on the table, trimmed to the iterations run
+        hist["links_up"] = [int(v) for v in links_up(link_table[:iters_done])]
+        hist["link_age_max"] = [int(v) for v in link_age_max(link_table[:iters_done])]
     if timing is not None:
         import time
         timing["loop_s"] = time.perf_counter() - t_loop
@@ -388,7 +427,8 @@ def run_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn, N, lam_tv=0.01, r
         timing["V_total"] = V_total
     if write_params and rank == 0:
         _write_params(snapshot_dir, rho_k, lam_tv, V_total, mu, tv_iters, cg_iters, relaxation,
-                      (rho, adapt, rho_changes) if adapt is not None else None, fuse, robust)
+                      (rho, adapt, rho_changes) if adapt is not None else None, fuse, robust,
+                      describe(links, link_table[:iters_done]) if link_table is not None else None)
     if inspect is not None:
         inspect(rg)
     if fuse is not None and fuse_out is not None:  # the returned images' fusion and spread: after the loop's clock
@@ -642,8 +682,8 @@ def _snapshot(snapshot_dir, k, rg, N):
 
 
 def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxation=None, balancing=None, fuse=None,
-                  robust=None):
-    """_ver2:291-306 admm_internal_params.txt (a relaxed run adds its alpha; a run with residual
+                  robust=None, links=None):
+    """_ver2:291-306 admm_internal_params.txt (``links``: the schedule's line, links.describe; a relaxed run adds its alpha; a run with residual
     balancing passes the rho its last iteration ran with and ``balancing`` = (rho_0, the checked
     adapt_rho configuration, the number of changes), which becomes one more line)."""
     try:
@@ -675,6 +715,8 @@ def _write_params(snapshot_dir, rho, lam_tv, V, mu, tv_iters, cg_iters, relaxati
             elif robust is not None:
                 f.write(f"Huber data term: delta = {robust['delta']}, reweighted every = {robust['every']}, "
                         f"until = {robust['until']}\n")
+            if links is not None:
+                f.write(links + "\n")
             f.write(f"Date-Time: {datetime.now().strftime('%Y-%m-%d %H:%M:%S')}\n")
     except Exception as e:  # pragma: no cover
         print(f"[WARN] Could not save internal params: {e}")

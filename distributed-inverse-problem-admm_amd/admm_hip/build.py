@@ -11,7 +11,7 @@ PKG = os.path.dirname(_HERE)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(_HERE, "libadmm_tomo.so")
 SOURCES = ["admm_tomo.hip", "masks.hip", "fbp.hip", "metrics.hip", "bounds.hip", "relax.hip", "norms.hip",
-           "fuse.hip", "robust.hip", "scale.hip"]
+           "fuse.hip", "robust.hip", "scale.hip", "links.hip"]
 DEPS = SOURCES + ["kernels.hpp", "tables.hpp", "fwd_plan.hpp", "common.hpp"]
 
 

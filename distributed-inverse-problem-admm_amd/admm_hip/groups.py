@@ -35,6 +35,7 @@ from .plan import STORED_Z_HBM_FRACTION, ShardPlan, make_plan, make_subset_plan,
 from .bounds import BOUND_KEYS, BOUND_STATS, check_bound_run, check_bound_weight, check_bounds
 from .fuse import FUSE_KEYS, FUSE_SCALARS, TERM_W, TERM_WD2, TERM_WX, FixedSum, Fuser, check_fuse
 from .penalty import NORM_KEYS, NORM_STATS, check_tolerance_run
+from .links import check_links_run
 from .relax import check_relaxation, check_relaxed_run
 from .solver import NodeBatch
 from .table import NodeColumns
@@ -144,8 +145,12 @@ class RankGroups:
     def __init__(self, A_list, G, V_total: int, world: int, rank: int, sinograms, Qij_diag_fn,
                  rho, lam, mu, tv_iters, cg_iters, tv_kind, phantom, fusion="midpoint", Wi_list=None,
                  keep_x=False, group=None, halo=True, streams=1, derive_z=None,
-                 stop_norms=False, relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
-        """``stop_norms``: the run takes the three norms of the scale-free stop test after every
+                 stop_norms=False, links=None, relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
+        """``links``: None or the run's bool table (iterations, global edges) (links.schedule): every batch gets
+        a gate (links.Gate) holding its stored edges' columns, so an edge stored by two batches or two ranks is
+        gated alike; ``set_link_row(k)`` before ``exchange_consensus`` picks the iteration.  It needs stored z:
+        derived z -- forced, or chosen by the HBM rule -- raises ValueError on every rank alike.
+        ``stop_norms``: the run takes the three norms of the scale-free stop test after every
         iteration (``node_norms``; run_admm's eps_abs / eps_rel): three more node columns, and stored z
         -- derived z, forced or chosen by the HBM rule, raises ValueError on every rank alike.
         ``relaxation``: None or alpha in (0, 2): every batch's edge updates and projection run
@@ -174,6 +179,10 @@ class RankGroups:
         check_bound_run(self.bounds, fusion, edge_state, forced)
         self.relaxation = check_relaxation(relaxation)
         check_relaxed_run(self.relaxation, edge_state, forced)
+        check_links_run(links, edge_state, forced)
+        if links is not None and tuple(links.shape[1:]) != (len(self.plan.edges),):
+            raise ValueError(f"links: the table has shape {tuple(links.shape)}, the graph has "
+                             f"{len(self.plan.edges)} edges")
         self.stop_norms = bool(stop_norms)
         check_tolerance_run(True if self.stop_norms else None, edge_state, forced)
         if not self.plan.local_nodes:
@@ -213,7 +222,8 @@ class RankGroups:
         if derive_z is None and fusion == "midpoint":
             derive_z = not z_is_stored(stored_edges_per_rank(A_list, G, V_total, world, streams,
                                                              bound_slots=self.bounds is not None), n0, hbm, fusion)
-            need_stored_z(derive_z, self.bounds is not None, self.relaxation is not None, "run", self.stop_norms)
+            need_stored_z(derive_z, self.bounds is not None, self.relaxation is not None, "run", self.stop_norms,
+                          links=links is not None)
         self.derive_z = bool(derive_z) if derive_z is not None else False
         devices = {k[0][2] for k in keys}
         if len(devices) > 1:
@@ -231,7 +241,7 @@ class RankGroups:
                                           cg_iters, tv_kind, phantom, device, fusion=fusion, Wi_list=Wi_list,
                                           keep_x=keep_x, derive_z=self.derive_z, ray_weights=ray_weights,
                                           bounds=self.bounds, bound_weight=bound_weight,
-                                          relaxation=self.relaxation))
+                                          relaxation=self.relaxation, links=links))
         self.device = self.batches[0].dev
         if len(self.batches) == 1:
             self.x_rank = self.batches[0].x_ext
@@ -301,6 +311,13 @@ class RankGroups:
 
     def consensus(self) -> None:
         self._concurrent(lambda nb: nb.consensus())
+
+    def set_link_row(self, k: int) -> None:
+        """Iteration ``k``'s gates for every batch's next edge updates (a run with ``links``; host arithmetic
+        on a pointer, no device work).  Call before ``exchange_consensus``."""
+        for nb in self.batches:
+            if nb.gate is not None:
+                nb.gate.set_row(k)
 
     def set_rho(self, rho: float) -> None:
         """Every batch's penalty <- ``rho`` (NodeBatch.set_rho: the scaled duals rescaled, the library's

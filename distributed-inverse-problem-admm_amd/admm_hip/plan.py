@@ -222,8 +222,9 @@ def derived_z_requested(edge_state, env_edge_state: str = "") -> bool:
     return edge_state == "derived" or (edge_state is None and env_edge_state == "derived")
 
 
-def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str, tolerances: bool = False) -> None:
-    """Bounds, relaxation and the scale-free stop test (``tolerances``: eps_abs / eps_rel) need stored
+def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str, tolerances: bool = False,
+                  links: bool = False) -> None:
+    """Bounds, relaxation, unreliable links and the scale-free stop test (``tolerances``: eps_abs / eps_rel) need stored
     z: ValueError where the rule above chose derived z for ``scope`` ("run" / "batch"); the bounds'
     message first, as the constraint rows count as edges."""
     if derive_z and bounded:
@@ -234,4 +235,7 @@ def need_stored_z(derive_z: bool, bounded: bool, relaxed: bool, scope: str, tole
                          "rule (plan.z_is_stored)")
     if derive_z and tolerances:
         raise ValueError(f"eps_abs / eps_rel need stored z, and this {scope}'s edge state does not fit the stored-z "
+                         "rule (plan.z_is_stored)")
+    if derive_z and links:
+        raise ValueError(f"links need stored z, and this {scope}'s edge state does not fit the stored-z "
                          "rule (plan.z_is_stored)")

@@ -27,6 +27,7 @@ from . import _lib
 from .bounds import BoundProjector, check_bound_run, check_bound_weight, check_bounds
 from .geometry import (CSR_WEIGHTS_MSG, ParallelBeamGeometry, RayTransform, current_stream_handle,
                        ray_weights_host, _Ctx)
+from .links import Gate
 from .penalty import NodeNorms
 from .plan import ShardPlan, need_stored_z, z_is_stored
 from .relax import Relaxer, check_relaxation, check_relaxed_run
@@ -65,8 +66,14 @@ class NodeBatch:
                  Qij_diag_fn, rho: float, lam: float, mu: float, tv_iters: int = 10,
                  cg_iters: int = 5, tv_kind: str = "iso", phantom=None, device: int = 0,
                  fusion: str = "midpoint", Wi_list=None, keep_x: bool = False, derive_z: bool | None = None,
-                 relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
-        """``relaxation``: None or alpha in (0, 2) (relax.check_relaxation; 1.0 is None): the edge
+                 links=None, relaxation=None, bounds=None, bound_weight=None, ray_weights=None):
+        """``links``: None or a bool table (iterations, global edges) (links.schedule): the edge updates of
+        ``consensus`` and ``consensus_range`` go through the gate (links.Gate, admm_consensus_gated), which reads
+        row ``gate.row`` of the table on the device: an up edge is updated as ever (relaxed if ``relaxation``
+        is set, either fusion), a down edge keeps y, z (and y_b) bit for bit.  The bound projection stays as it
+        is.  Needs stored z.  None: nothing changes, no buffer.
+
+        ``relaxation``: None or alpha in (0, 2) (relax.check_relaxation; 1.0 is None): the edge
         updates and the constraint's projection run over-relaxed, around alpha x + (1 - alpha) z_old
         (admm_consensus_relaxed / admm_bound_project_relaxed through ``consensus``, ``consensus_range``
         and ``bound_project``; either fusion).  Needs stored z.  None: nothing changes, no buffer.
@@ -109,6 +116,8 @@ class NodeBatch:
         kappa = check_bound_weight(bound_weight, self.bounds)
         alpha = check_relaxation(relaxation)
         check_relaxed_run(alpha, "derived" if derive_z else None)
+        if links is not None and derive_z:
+            raise ValueError("links need stored z: a derived z has no per-edge age")
         check_bound_run(self.bounds, fusion, "derived" if derive_z else None)
         if self.bounds is not None and Wi_list is None:
             raise ValueError("bounds need Wi_list: q_c,i = bound_weight * Wi_list[i]")
@@ -185,7 +194,7 @@ class NodeBatch:
         if derive_z is None:
             hbm = int(torch.cuda.get_device_properties(dev).total_memory)
             derive_z = not z_is_stored([ES], n, hbm, fusion)
-            need_stored_z(derive_z, bool(NB), alpha is not None, "batch")
+            need_stored_z(derive_z, bool(NB), alpha is not None, "batch", links=links is not None)
         if derive_z and fusion != "midpoint":
             raise ValueError("derived z needs midpoint fusion")
         self.derive_z = bool(derive_z)
@@ -211,6 +220,8 @@ class NodeBatch:
         self.bound_stats = self.projector.sums if NB else None  # (V, BOUND_STATS), written by the kernel
         # over-relaxation: alpha and the relaxed edge kernel's scratch (None: the plain updates)
         self.relaxer = Relaxer(alpha, n, E, dev) if alpha is not None else None
+        # unreliable links: the gate table in slot order, alpha and the gated kernel's scratch (None: every edge up)
+        self.gate = Gate(links, plan.stored_edges, n, dev, alpha) if links is not None else None
         # the stop test's three norms per node (node_norms): scratch and sums made at the first call
         self.norms = None
         self.norm_stats = None
@@ -454,7 +465,11 @@ class NodeBatch:
             t.index_copy_(0, idx, s)
 
     def consensus(self) -> None:
-        if self.relaxer is not None:  # every real edge (either fusion), then the constraint slots
+        if self.gate is not None:  # every real edge under the current row's gates, then the constraint slots
+            self.gate.run_edges(self, 0, self.n_real_edges, self._s())
+            if self.bounds is not None:
+                self.bound_project()
+        elif self.relaxer is not None:  # every real edge (either fusion), then the constraint slots
             self.relaxer.run_edges(self, 0, self.n_real_edges, self._s())
             if self.bounds is not None:
                 self.bound_project()
@@ -492,10 +507,10 @@ class NodeBatch:
             top = max(max(self.plan.edge_a_row[e0:e1]), max(self.plan.edge_b_row[e0:e1]))
             if top >= rows:
                 raise ValueError(f"edge slots [{e0}, {e1}) reach x_ext row {top} >= rows={rows}")
-            if self.relaxer is not None:
+            if self.gate is not None or self.relaxer is not None:
                 if self.fusion != "midpoint":
                     raise ValueError("consensus_range needs midpoint fusion")
-                self.relaxer.run_edges(self, e0, e1, self._s())
+                (self.gate or self.relaxer).run_edges(self, e0, e1, self._s())
                 return
             _lib.check(self.lib.admm_consensus_range(self.ctx.h, int(e0), int(e1), int(rows), C.c_void_p(self._s())),
                        "admm_consensus_range")

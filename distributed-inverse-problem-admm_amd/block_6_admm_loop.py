@@ -55,6 +55,12 @@ Beyond the reference's surface:
                 (h = min(1, delta / |A x - b|) times ``ray_weights``); adds the history keys
                 robust_loss_per_node / robust_loss_total, robust_outliers_per_node /
                 robust_outliers_total; geometry operators only (admm_hip/admm.py, admm_hip/robust.py)
+* ``links``     None (default), a probability p in (0, 1], a dict (p, seed, max_age, outages) or a bool array
+                (iterations, edges): unreliable links.  In every iteration each edge of G is up -- its z / y
+                update runs as ever -- or down: it keeps y and z, and both endpoints go on with the last
+                values they hold.  Converges to the same fixed point in about 1 / p times the iterations;
+                adds the history keys links_up and link_age_max; needs stored z (admm_hip/admm.py,
+                admm_hip/links.py)
 """
 from __future__ import annotations
 
@@ -81,7 +87,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        scs_save_every_chunks=1,
                        mu=None, tv_iters=None, cg_iters=5, tv_kind="iso", group=None,
                        phantom_true=None, write_params=True, fuse=None, fuse_out=None, robust=None,
-                       adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
+                       links=None, adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None, bounds=None,
                        bound_weight=None, return_feasible=False, ray_weights=None):
     del scs_use_indirect, scs_eps, scs_alpha, scs_acceleration, scs_lookback, scs_scale
     cg = int(cg_iters)
@@ -99,7 +105,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        chunk_save_every=scs_save_every_chunks, ray_weights=ray_weights, bounds=bounds,
                        bound_weight=bound_weight, return_feasible=return_feasible, relaxation=relaxation,
                        adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel, fuse=fuse, fuse_out=fuse_out,
-                       robust=robust)
+                       robust=robust, links=links)
     hist["primal_res"] = hist["primal"]
     hist["dual_res"] = hist["dual"]
     hist["obj"] = hist["obj_total"]

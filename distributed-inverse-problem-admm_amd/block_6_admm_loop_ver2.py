@@ -64,6 +64,12 @@ updates run on MI355X (admm_hip.admm.run_admm).  Extra keyword arguments:
                 (h = min(1, delta / |A x - b|) times ``ray_weights``); adds the history keys
                 robust_loss_per_node / robust_loss_total, robust_outliers_per_node /
                 robust_outliers_total; geometry operators only (admm_hip/admm.py, admm_hip/robust.py)
+* ``links``     None (default), a probability p in (0, 1], a dict (p, seed, max_age, outages) or a bool array
+                (iterations, edges): unreliable links.  In every iteration each edge of G is up -- its z / y
+                update of :210-230 runs as ever -- or down: it keeps y and z, and both endpoints go on with
+                the last values they hold.  Converges to the same fixed point in about 1 / p times the
+                iterations; adds the history keys links_up and link_age_max; needs stored z
+                (admm_hip/admm.py, admm_hip/links.py)
 
 ``max_inner_iters`` is accepted and, as in the reference, unused.
 """
@@ -81,7 +87,7 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                        mu=None, tv_iters=10, cg_iters=5, tv_kind="iso", group=None,
                        write_params=True, fusion="midpoint", inner_tol=None,
                        max_inner_updates=10, x_init=None, fuse=None, fuse_out=None, robust=None,
-                       metrics=None, data_range=None, metrics_mask=None,
+                       links=None, metrics=None, data_range=None, metrics_mask=None,
                        adapt_rho=None, eps_abs=None, eps_rel=None, relaxation=None,
                        bounds=None, bound_weight=None,
                        return_feasible=False, ray_weights=None):
@@ -97,4 +103,4 @@ def decentralized_admm(A_dense_list, sinograms, G, Wi_list, Qij_diag_fn,
                     data_range=data_range, metrics_mask=metrics_mask, ray_weights=ray_weights,
                     bounds=bounds, bound_weight=bound_weight, return_feasible=return_feasible,
                     relaxation=relaxation, adapt_rho=adapt_rho, eps_abs=eps_abs, eps_rel=eps_rel,
-                    fuse=fuse, fuse_out=fuse_out, robust=robust)
+                    fuse=fuse, fuse_out=fuse_out, robust=robust, links=links)

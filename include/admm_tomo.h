@@ -412,6 +412,28 @@ int admm_bound_project_relaxed(const double* x, long long x_stride, double* w, d
                                const double* lo_map, const double* hi_map, double lo, double hi, long long n,
                                int nimg, double alpha, double* work, double* out, void* stream);
 
+/* --- unreliable links: the gated edge update --- */
+
+/* The stored-z edge update of the slots [e0, e1) with one gate per slot: up[e] != 0 (slot e is up) or
+ * up[e] == 0 (down); `up` is a device array of at least e1 bytes, indexed by the absolute slot.
+ *   up:    exactly the update of admm_consensus (alpha == 1.0) or of admm_consensus_relaxed (any other
+ *          alpha), operation for operation, either fusion (y_b, w both null or both set, as there);
+ *   down:  y, z (and y_b) rows of the slot are not written; edge_stats[e] = { sum (x_a - z)^2,
+ *          sum (x_b - z)^2, +0.0 } with the z the slot holds.
+ * edge_stats rows e0 .. e1 - 1 are written; nothing else outside the up slots' y, z (y_b) rows is.  An edge
+ * with an endpoint row outside [0, n_rows) is left unchanged and its statistics are NaN, up or down.
+ * Layout of admm_consensus_relaxed: 1024 pixels per block, one edge per blockIdx.y, 8-byte accesses, 48 B
+ * per pixel of an up edge and 24 B of a down edge; no atomics: per-(edge, block) partial sums in fixed
+ * slots of `work` (admm_consensus_gated_work doubles for at least e1 edges, caller-owned), then one
+ * fixed-order sum per edge.  0 < alpha < 2, finite.  Context-free, allocates nothing, asynchronous on
+ * `stream` (current device).  Additive: ADMM_ABI_VERSION stays 9. */
+int admm_consensus_gated(const double* x_ext, long long n, int n_rows, double* y, double* y_b, double* z,
+                         const double* w, const int32_t* edge_a, const int32_t* edge_b, int e0, int e1,
+                         double alpha, const uint8_t* up, double* work, double* edge_stats, void* stream);
+/* *n_doubles = the doubles of `work` admm_consensus_gated needs for n pixels and n_edges edge slots
+ * (e1 <= n_edges).  No device work. */
+int admm_consensus_gated_work(long long n, int n_edges, long long* n_doubles);
+
 /* --- residual-balancing rho and the scale-free stop test --- */
 
 /* rho of the bound batch <- rho, finite and > 0 (ADMM_E_INVALID otherwise; ADMM_E_STATE without a bound
